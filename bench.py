@@ -19,12 +19,20 @@ the m-vector partial A_g*(B_g*q) per Arnoldi step (strong scaling; value = GMRES
 iterations of the global solve / max rank time).  `--replicas` instead runs one
 independent solve per GPU (weak scaling, no collective).
 
-Extra fields: "roofline" for the dominant SpMV kernel (algorithmic bytes per
-launch / average launch duration from HIP events recorded on the library's
-stream during the timed region), "kernels" (both SpMV classes and MGS),
-"cpu_baseline" (the oracle restatement timed on the host cores, rank 0, N=1: the process's
-OMP_NUM_THREADS share of the cores through oracle/spmv_omp.c -- 16 on the 1-GPU box -- plus a
-one-core scipy leg; thread count, its reason, nproc and CPU model stated).
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  Extra fields:
+"roofline" for the dominant SpMV kernel (algorithmic bytes per launch / average launch
+duration from HIP events recorded on the library's stream during the timed region) and
+"kernels" (both SpMV classes and MGS): they ride in the timed steps and take no run of their own.
+`--full` adds what takes runs of its own: "cpu_baseline" (the oracle restatement timed on the
+host cores, rank 0, N=1: the process's OMP_NUM_THREADS share of the cores through
+oracle/spmv_omp.c, plus a one-core scipy leg; thread count, its reason, nproc and CPU model
+stated); without `--full` the field is null.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(float64): x (a fixed seeded sample of it, with the sampled positions, where x is large),
+error_norm, residual_norm, niters, and ar_hist / gcv_lambda where the workload has them.  The
+inputs are generated from fixed seeds, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -92,7 +100,13 @@ def parse():
                          "monitor to the x-forming reconstruction on the step stream: not the global solve's path)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="experiment: per-context numerics option (hgm_ctx_set_option), e.g. mgs_fused=0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the cpu_baseline legs (the oracle "
+                         "restatement timed on the host cores)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (x or a fixed seeded sample of it, "
+                         "the histories, niters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline legs")
     ap.add_argument("--no-timing", action="store_true", help="disable per-kernel HIP-event timing")
     # default A: the roofline kernel; timing both classes costs ~11% of the C2 step, A alone ~4%
     ap.add_argument("--time-classes", default="A", choices=["A", "B", "AB", "MGS", "ALL"],
@@ -427,8 +441,16 @@ def main():
                                        f"passes (gfx950 wide-read correction), committed -- not counters of this "
                                        f"run; frac_traffic = traffic / avg_launch_us / peak")
 
+    if args.dump_outputs:
+        out = {"x": x_d.cpu().numpy(), "error_norm": err, "residual_norm": res, "niters": [it.value]}
+        if wl["solver"] == "lsmr_solver":
+            out["ar_hist"] = arh
+        if chosen:
+            out["gcv_lambda"] = [chosen["lam"]]
+        dump_outputs(args.dump_outputs, out, rank, world)
+
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(A, B, b, x_true, wl, args.cpu_iters or wl["cpu_iters"],
                            0 if args.no_cpu_single else wl.get("cpu_iters_single", wl["cpu_iters"]))
 
@@ -476,6 +498,27 @@ def main():
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_X_MAX = 1 << 21        # x is written whole up to this length, as a sample of this many above it
+
+
+def dump_outputs(d, out, rank, world):
+    """Write the last timed step's outputs as d/<name>.npy, float64 (ranks past the first of a
+    multi-GPU run add _rank<r> to the name: each holds its own pixels of x).  An x longer than
+    DUMP_X_MAX goes out as x_sample, its values at DUMP_X_MAX positions drawn once from a fixed
+    seed, next to the positions (x_sample_index): 32 MiB for the two at any size."""
+    os.makedirs(d, exist_ok=True)
+    out = dict(out)
+    x = out.pop("x")
+    if x.size > DUMP_X_MAX:
+        idx = np.sort(np.random.default_rng(20240229).choice(x.size, DUMP_X_MAX, replace=False))
+        out["x_sample"], out["x_sample_index"] = x[idx], idx
+    else:
+        out["x"] = x
+    sfx = f"_rank{rank}" if world > 1 and rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def _cpu_model():

@@ -5,11 +5,12 @@
 # Outputs go to gpurun_out/$TAG/ (TAG defaults to r4); the file each recipe writes is the one
 # copied to profiles/ under the name given below (profiles/README.md lists them).
 #
-#   evidence                 GPU tests, smoke, the default bench line, the rocprofv3 kernel-trace
+#   evidence                 GPU tests, smoke, the default bench line (--full), the rocprofv3 kernel-trace
 #                            summary of the same command
 #                            -> $TAG_gpu_tests.log, $TAG_bench_default_c4.json, $TAG_default_kernel_stats.csv
 #   tests [PYTEST_ARGS]      pytest -m gpu (e.g. tests/test_gpu_fused.py -k gkb) -> $TAG_gpu_tests_<n>.log
-#   bench WL [BENCH_ARGS]    one bench line of workload WL (c2 c3 c3gcv c4 c5 c5m) -> $TAG_bench_<wl>.json
+#   bench WL [BENCH_ARGS]    one bench line (bench.py --full: with its cpu_baseline) of workload WL
+#                            (c2 c3 c3gcv c4 c5 c5m) -> $TAG_bench_<wl>.json
 #   trace WL [BENCH_ARGS]    rocprofv3 --kernel-trace --stats of that bench -> $TAG_<wl>_kernel_stats.csv
 #   traffic WL [BENCH_ARGS]  FETCH_SIZE / WRITE_SIZE passes (one counter per run) + the per-kernel
 #                            HBM-bytes summary (gfx950 x2 FETCH correction) -> traffic_<NAME or wl>.json
@@ -42,7 +43,7 @@ case "$recipe" in
         > "$O/${TAG}_gpu_tests.log" 2>&1 || { tail -40 "$O/${TAG}_gpu_tests.log"; exit 1; }
     tail -3 "$O/${TAG}_gpu_tests.log"
     timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || exit 1
-    timeout -k 10 600 python bench.py --gpus 1 > "$O/bench_default.log" 2>&1 || { tail -20 "$O/bench_default.log"; exit 1; }
+    timeout -k 10 600 python bench.py --gpus 1 --full > "$O/bench_default.log" 2>&1 || { tail -20 "$O/bench_default.log"; exit 1; }
     bench_line "$O/bench_default.log" > "$O/${TAG}_bench_default_c4.json"
     cat "$O/${TAG}_bench_default_c4.json"
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_default" -o trace \
@@ -78,7 +79,7 @@ case "$recipe" in
     ;;
   bench)
     wl=$1; shift
-    timeout -k 10 600 python -u bench.py --workload "$wl" "$@" > "$O/bench_$wl.log" 2>&1 || { tail -20 "$O/bench_$wl.log"; exit 1; }
+    timeout -k 10 600 python -u bench.py --full --workload "$wl" "$@" > "$O/bench_$wl.log" 2>&1 || { tail -20 "$O/bench_$wl.log"; exit 1; }
     bench_line "$O/bench_$wl.log" | tee "$O/${TAG}_bench_$wl.json"
     ;;
   trace)
@@ -146,7 +147,7 @@ print(json.dumps({'round': $r, 'side': $side, 'args': '''$args''', 'value': d['v
     cat "$O/${TAG}_lib_ab.jsonl"
     ;;
   *)
-    sed -n 2,28p "$0"
+    sed -n 2,29p "$0"
     exit 2
     ;;
 esac

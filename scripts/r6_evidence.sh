@@ -15,14 +15,14 @@ case "$1" in
     cat $O/${T}_smoke.txt | grep smoke
     ;;
   B)
-    timeout -k 10 600 python -u bench.py > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
+    timeout -k 10 600 python -u bench.py --full > $O/bench_default.log 2>&1 || { tail -20 $O/bench_default.log; exit 1; }
     bench_line $O/bench_default.log > $O/${T}_bench_default_c4.json; cat $O/${T}_bench_default_c4.json | cut -c1-300
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_default -o trace \
         -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline > $O/trace_default.log 2>&1 || exit 1
     bench_line $O/trace_default.log > $O/${T}_bench_default_c4_traced.json
     cp "$(find $O/trace_default -name '*kernel_stats.csv' | head -1)" $O/${T}_default_kernel_stats.csv
     for wl in c2 c3 c3gcv c5 c5m; do
-      timeout -k 10 600 python -u bench.py --workload $wl > $O/bench_$wl.log 2>&1 || { tail -20 $O/bench_$wl.log; exit 1; }
+      timeout -k 10 600 python -u bench.py --full --workload $wl > $O/bench_$wl.log 2>&1 || { tail -20 $O/bench_$wl.log; exit 1; }
       bench_line $O/bench_$wl.log > $O/${T}_bench_$wl.json; cut -c1-200 $O/${T}_bench_$wl.json
     done
     ;;

@@ -18,7 +18,18 @@ def pytest_configure(config):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+    """The fixture's arrays.  An array too large for one committed file lies next to it in
+    consecutive pieces, piece i as <stem>.<key>.<i>.npz (make_golden.py save_golden): joined here."""
+    import glob
+    g = dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+    stem = os.path.join(GOLDEN, name[:-len(".npz")])
+    pieces = {}
+    for p in glob.glob(glob.escape(stem) + ".*.*.npz"):
+        key, i = p[len(stem) + 1:-len(".npz")].rsplit(".", 1)
+        pieces.setdefault(key, {})[int(i)] = np.load(p, allow_pickle=False)[key]
+    for key, ps in pieces.items():
+        g[key] = np.concatenate([ps[i] for i in range(len(ps))])
+    return g
 
 
 def golden_problem(name):

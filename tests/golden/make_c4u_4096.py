@@ -25,7 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "hybrid-gmres_amd"), ROOT, os.path.join(ROOT, "tests", "golden")]
-from make_golden import csr_hash  # noqa: E402
+from make_golden import csr_hash, save_golden  # noqa: E402
 
 
 def main(out, k=20, N=4096, na=47):
@@ -73,9 +73,9 @@ def main(out, k=20, N=4096, na=47):
     b = b_exact + e / np.linalg.norm(e) * 1e-2 * np.linalg.norm(b_exact)
     x, err, res, kk, H = R.ABgmres_nonhybrid_bounds(PA, PB, b, xt, 0.0, k, return_H=True)
     st = 997
-    np.savez_compressed(out, maxit=k, N=N, n_angles=na, A_sha256=hA, B_sha256=hB, b=b, sample_stride=st,
-                        abn_H=H, abn_err=err, abn_res=res, abn_k=kk, abn_xnorm=np.linalg.norm(x),
-                        abn_xs=x[::st].copy())
+    save_golden(out, dict(maxit=k, N=N, n_angles=na, A_sha256=hA, B_sha256=hB, b=b, sample_stride=st,
+                          abn_H=H, abn_err=err, abn_res=res, abn_k=kk, abn_xnorm=np.linalg.norm(x),
+                          abn_xs=x[::st].copy()))
     stop.set()
     print(f"wrote {out}: k {kk} res {res[-1]:.6e} err {err[-1]:.6e}, {time.time() - t0:.0f} s", flush=True)
 

@@ -22,6 +22,38 @@ from oracle import restatement as R       # noqa: E402
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
+PIECE_BYTES = 640 * 1024     # noise-carrying float64 hardly compresses: a piece stays under 1 MiB on disk
+
+
+def save_golden(path, d):
+    """np.savez_compressed(path, **d), with every 1-D array above PIECE_BYTES cut into consecutive
+    pieces, piece i as the array <key> of <stem>.<key>.<i>.npz next to the main file (no committed
+    file above 1 MiB).  tests/conftest.py load_golden and load_golden_file below join them again."""
+    main, stem = {}, path[:-len(".npz")]
+    for key, a in d.items():
+        a = np.asarray(a)
+        if a.ndim == 1 and a.nbytes > PIECE_BYTES:
+            for i, piece in enumerate(np.array_split(a, -(-a.nbytes // PIECE_BYTES))):
+                np.savez_compressed(f"{stem}.{key}.{i}.npz", **{key: piece})
+        else:
+            main[key] = a
+    np.savez_compressed(path, **main)
+
+
+def load_golden_file(path):
+    """The arrays save_golden wrote, pieces joined."""
+    import glob
+    g = dict(np.load(path, allow_pickle=False))
+    stem = path[:-len(".npz")]
+    pieces = {}
+    for p in glob.glob(glob.escape(stem) + ".*.*.npz"):
+        key, i = p[len(stem) + 1:-len(".npz")].rsplit(".", 1)
+        pieces.setdefault(key, {})[int(i)] = np.load(p, allow_pickle=False)[key]
+    for key, ps in pieces.items():
+        g[key] = np.concatenate([ps[i] for i in range(len(ps))])
+    return g
+
+
 def csr_hash(M):
     """sha256 over indptr (int64), indices (int32), data (float64), without copying the arrays
     (the C4 operator is 12 GB)."""
@@ -133,7 +165,7 @@ def dump_c4(name="c4_4096.npz", k=20):
     d = {"maxit": k, "N": 4096, "n_angles": 47, "A_sha256": h, "b": b, "sample_stride": 997,
          "abn_H": H, "abn_err": err, "abn_res": res, "abn_k": kk, "abn_xnorm": np.linalg.norm(x),
          "abn_xs": x[::997].copy()}
-    np.savez_compressed(os.path.join(OUT, name), **d)
+    save_golden(os.path.join(OUT, name), d)
     print("wrote", name, "k", kk, "res", res[-1], "err", err[-1])
 
 
@@ -195,7 +227,7 @@ def dump_c5(name="c5_4096.npz", k=20, stride=197):
     import scipy.sparse as sp
     from oracle import parallel as OP
     from hgmres.problems import siddon_projector, shepp_logan
-    g = np.load(os.path.join(OUT, "c4_4096.npz"))
+    g = load_golden_file(os.path.join(OUT, "c4_4096.npz"))
     b = np.ascontiguousarray(g["b"])
     A = siddon_projector(4096, 47)
     h64 = csr_hash(A)
@@ -288,7 +320,7 @@ def dump_c4u(name="c4u_2048.npz", k=20):
     d = {"maxit": k, "N": 2048, "n_angles": 47, "A_sha256": hA, "B_sha256": hB, "b": b, "sample_stride": 997,
          "abn_H": H, "abn_err": err, "abn_res": res, "abn_k": kk, "abn_xnorm": np.linalg.norm(x),
          "abn_xs": x[::997].copy()}
-    np.savez_compressed(os.path.join(OUT, name), **d)
+    save_golden(os.path.join(OUT, name), d)
     print("wrote", name, "k", kk, "res", res[-1], "err", err[-1])
 
 
