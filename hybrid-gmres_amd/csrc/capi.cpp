@@ -40,6 +40,10 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
                 double* res_out, int* niters);
 int arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const double* b_in, int kg, int side, double btol,
             int orth, double* H_out, double* beta_out, int* kdone);
+int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b_in,
+                       const double* xt_in, double tol, int maxit, const double* lambdas, int nlam, int side,
+                       double* X_out, double* err_surf, double* res_surf, double* sol_surf, int* niters,
+                       int* ksteps);
 // bounds.cpp
 int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
                         const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
@@ -1008,6 +1012,46 @@ HGM_API int hgm_spmv_ab(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const vo
     return HGM_OK;
 }
 
+HGM_API int hgm_proj_norms(hgm_ctx* c, int64_t rows, int k, const double* V, int64_t ldv, const double* Y,
+                           int64_t ldy, int nlam, const double* t, double* sumsq_diff, double* sumsq) {
+    if (!c || !V || !Y || !sumsq_diff) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_HIP(hipSetDevice(c->device));
+        HGM_REQUIRE(nlam >= 1, "proj_norms: at least one column");
+        double* out = c->buf<double>("pn_out", (size_t)2 * nlam);
+        hipEvent_t tm;
+        timing_begin(c, KC_PNORM, &tm);
+        proj_norms<double>(c, rows, k, V, ldv, Y, ldy, nlam, t, out, sumsq ? out + nlam : nullptr);
+        timing_end(c, KC_PNORM, tm, 8.0 * (double)rows * k);
+        Reader rd(c);
+        rd.add(sumsq_diff, out, sizeof(double) * nlam);
+        if (sumsq) rd.add(sumsq, out + nlam, sizeof(double) * nlam);
+        rd.go();
+    });
+    return HGM_OK;
+}
+
+HGM_API int hgm_proj_norms_loop(hgm_ctx* c, int64_t rows, int k, const double* V, int64_t ldv, const double* Y,
+                                int64_t ldy, int nlam, const double* t, double* sumsq_diff) {
+    if (!c || !V || !Y || !t || !sumsq_diff) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_HIP(hipSetDevice(c->device));
+        HGM_REQUIRE(nlam >= 1 && rows >= 1 && k >= 1 && ldv >= rows && ldy >= k, "proj_norms_loop: bad dimensions");
+        double* out = c->buf<double>("pn_out", (size_t)2 * nlam);
+        hipEvent_t tm;
+        timing_begin(c, KC_PNORM, &tm);
+        // the residual-only form of the solvers' reconstruction launch (x == nullptr), once per column
+        for (int l = 0; l < nlam; ++l)
+            recon<double>(c, 0, k, nullptr, 2, Y + (int64_t)l * ldy, nullptr, nullptr, nullptr, rows, V, ldv, t,
+                          out + l);
+        timing_end(c, KC_PNORM, tm, 8.0 * (double)rows * k * nlam);
+        Reader rd(c);
+        rd.add(sumsq_diff, out, sizeof(double) * nlam);
+        rd.go();
+    });
+    return HGM_OK;
+}
+
 HGM_API int hgm_fused_plan_info(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, double* build_s, uint64_t* checksum,
                                 int64_t* nslot, int* device_built) {
     if (!c || !A || !B) return HGM_E_ARG;
@@ -1084,6 +1128,13 @@ HGM_API int hgm_gmres_bounds_ex(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A,
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
     HGM_SOLVE(c, gmres_family(c, GmresSpec{side, hybrid ? PROJ_PTR : PROJ_LS, false, false}, o, A, B, b, xt, tol,
                               maxit, hybrid ? lambda : 0.0, x, err, res, niters));
+}
+HGM_API int hgm_gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
+                                   const double* xt, double tol, int maxit, const double* lambdas, int nlam, int side,
+                                   double* X, double* err, double* res, double* sol, int* niters, int* ksteps) {
+    if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
+    HGM_SOLVE(c, gmres_bounds_sweep(c, o, A, B, b, xt, tol, maxit, lambdas, nlam, side, X, err, res, sol, niters,
+                                    ksteps));
 }
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b,
                                const double* xt, double tol, int maxit, double* x, double* err, double* res,

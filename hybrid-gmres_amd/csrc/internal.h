@@ -56,14 +56,14 @@ struct DevBuf {
 };
 
 // Kernel classes timed by hgm_kernel_timing (bench roofline).
-enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_N = 4 };
+enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_N = 5 };
 
 struct Timing {
     bool on = false;
     bool paused = false;   // hgm_kernel_timing_pause: armed but not recording
     unsigned mask = 0xffu;   // timed classes
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[KC_N];
-    double bytes[KC_N] = {0, 0, 0, 0};
+    double bytes[KC_N] = {0, 0, 0, 0, 0};
     std::vector<hipEvent_t> pool;
     hipEvent_t get();
     void clear();
@@ -341,6 +341,14 @@ void gemv_err(hgm_ctx* c, int64_t n, int k, const T* Q, int64_t ldq, const T* y,
 template <typename T>
 void recon(hgm_ctx* c, int64_t n, int k, const T* Q, int64_t ldq, const T* y, T* x, const T* xt, T* err_out,
            int64_t m, const T* AQ, int64_t ldaq, const T* b, T* res_out);
+
+// Multi-coefficient projected norms (sweep.hip; the lambda sweep's monitors): for every column l < L
+// of Y (k x L, column-major, device), d_out[l] = sum_i ((V Y)_il - t_i)^2 and, when s_out != nullptr,
+// s_out[l] = sum_i (V Y)_il^2 over the rows of V (rows x k, ldv >= rows), in one pass over V; the
+// rows x L product is never stored.  t == nullptr: zeros.  Fixed summation order, no atomics.
+template <typename T>
+void proj_norms(hgm_ctx* c, int64_t rows, int k, const T* V, int64_t ldv, const T* Y, int64_t ldy, int L,
+                const T* t, T* d_out, T* s_out);
 
 // MGS sweep of v = Q(:,kk+1) against Q(:,0..kk); writes Hcol[0..kk+1] (device) and
 // normalises Q(:,kk+1) unless H(kk+1,kk) == 0.  dist: n-vectors sharded (scalar all-reduce

@@ -1666,6 +1666,183 @@ int arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const double* b_in, 
     return HGM_OK;
 }
 
+// ============================================================================
+// Lambda sweep of the hybrid PTR solvers: one Arnoldi for every lambda
+// ============================================================================
+// In ABgmres_hybrid_bounds.m:24-41 / BAgmres_hybrid_bounds.m:24-40 lambda enters only the k x k
+// projected solve yk = (Hk'*Hk + lambda*eye(k)) \ (Hk'*tk): Q, H and the kept products V = B*Q (AB)
+// or Q (BA) and W = A*B*Q (AB) or A*Q (BA) are the same for every lambda.  So the loop of
+// analyze_regularization.m:22-33 / plot_error_surface.m:28-42 (one solve per lambda) is one Arnoldi
+// here; iteration k solves the projected system for every lambda still running and gets all their
+// monitors ||b - W_k y_l||, ||V_k y_l - x_true|| and ||V_k y_l|| from two proj_norms passes.
+// Column l of every output is what hgm_gmres_bounds_ex(lambda = lambdas[l], hybrid = 1) returns
+// (breakdown convention included), entries past niters[l] are NaN.
+int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b_in,
+                       const double* xt_in, double tol, int maxit, const double* lambdas, int nlam, int side,
+                       double* X_out, double* err_surf, double* res_surf, double* sol_surf, int* niters,
+                       int* ksteps) {
+    check_dims(A, B);
+    solver_guard(c);
+    HGM_REQUIRE(B != nullptr, "B is NULL");
+    HGM_REQUIRE(b_in != nullptr, "b is required");
+    HGM_REQUIRE(A->dtype == HGM_F64, "lambda sweep: fp64 operators only");
+    if (dist_n(c) || c->host_ar != nullptr)
+        throw Error{HGM_E_UNSUPPORTED, "lambda sweep: single rank only (no communicator / all-reduce hook)"};
+    HGM_REQUIRE(!c->num.parity, "lambda sweep: not in parity mode");
+    HGM_REQUIRE(!(o && (o->flags & HGM_DEVICE_PTRS)), "lambda sweep: host buffers only (HGM_DEVICE_PTRS refused)");
+    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+    HGM_REQUIRE(nlam >= 1 && lambdas != nullptr, "lambda sweep: at least one lambda");
+    for (int l = 0; l < nlam; ++l)
+        HGM_REQUIRE(std::isfinite(lambdas[l]) && lambdas[l] >= 0.0, "lambda sweep: every lambda must be finite and >= 0");
+    HGM_REQUIRE(niters != nullptr, "niters is required");
+    const PixOrder po = n_order(c, A, B);
+    using T = double;
+    const int orth = o ? o->orth : HGM_MGS;
+    const int64_t m = A->rows, n = A->cols;
+    const bool nspace = side == HGM_SIDE_BA;
+    const int64_t dim = nspace ? n : m;
+    const int64_t ldq = krylov_ld(c, dim, false);
+    const int64_t ldaq = round_up(m > 0 ? m : 1, 64), ldbq = round_up(n > 0 ? n : 1, 64);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const size_t surf = (size_t)maxit * nlam;
+    if (err_surf) std::fill(err_surf, err_surf + surf, nan);
+    if (res_surf) std::fill(res_surf, res_surf + surf, nan);
+    if (sol_surf) std::fill(sol_surf, sol_surf + surf, nan);
+
+    T* Q = c->buf<T>("Q", (size_t)ldq * (maxit + 1));
+    if (krylov_padded(c, ldq)) HGM_HIP(hipMemsetAsync(Q, 0, sizeof(T) * ldq * (maxit + 1), c->stream));
+    // kept products: BA: W = A*Q ; AB: V = B*Q and W = A*B*Q
+    T* AQ = nspace ? c->buf<T>("AQ", (size_t)ldaq * maxit) : nullptr;
+    T* BQ = nspace ? nullptr : c->buf<T>("BQ", (size_t)ldbq * maxit);
+    T* ABQ = nspace ? nullptr : c->buf<T>("ABQ", (size_t)ldaq * maxit);
+    const T* V = nspace ? Q : BQ;
+    const int64_t ldv = nspace ? ldq : ldbq;
+    const T* W = nspace ? AQ : ABQ;
+    T* x = c->buf<T>("x", n > 0 ? n : 1);
+    T* Hd = c->buf<T>("H", (size_t)(maxit + 1) * maxit);
+    const int64_t ldy = maxit;
+    T* Yd[2] = {c->buf<T>("sweep_Y0", (size_t)ldy * nlam), c->buf<T>("sweep_Y1", (size_t)ldy * nlam)};
+    T* mon = c->buf<T>("sweep_mon", (size_t)4 * nlam);   // [res^2 | (W y)^2 | err^2 | (V y)^2]
+    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(T) * (maxit + 1) * maxit, c->stream));
+    const T* b = stage_in<T>(c, "in_b", b_in, m, false);
+    const T* xt = stage_in_n<T>(c, "in_xt", xt_in, n, false, po);
+
+    sumsq<T>(c, m, b, dslot<T>(c, S_NB));
+    if (xt) sumsq<T>(c, n, xt, dslot<T>(c, S_NXT));
+    // r0 (*_bounds.m:11-13): BA: B*(b - A*0) ; AB: b - A*(B*0)
+    if (nspace) apply_B<T>(c, B, b, Q, EPI_NONE, T(0), nullptr);
+    else HGM_HIP(hipMemcpyAsync(Q, b, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+    sumsq<T>(c, dim, Q, dslot<T>(c, S_BETA));
+    read_scalars(c, 0, 3);
+    const double nb = std::sqrt(c->hscal[S_NB]);
+    const double nxt = xt ? std::sqrt(c->hscal[S_NXT]) : 0.0;
+    const double beta = std::sqrt(c->hscal[S_BETA]);
+    div_scalar<T>(c, dim, Q, Q, (T)beta);
+
+    const FusedPlan* fplan = nspace ? nullptr : fused_ab_plan(c, A, B);
+    std::vector<double> H((size_t)(maxit + 1) * maxit, 0.0);
+    auto Hh = [&](int i, int j) -> double& { return H[(size_t)j * (maxit + 1) + i]; };
+    std::vector<char> active(nlam, 1);
+    int nactive = nlam;
+    std::vector<double> Yh((size_t)ldy * nlam), G, M, rhs, y, mh((size_t)4 * nlam);
+    // lambda l stops with iterate kx (0-based iteration; -1: x never assigned) after nit iterations
+    auto finish = [&](int l, int nit, int kx) {
+        active[l] = 0;
+        --nactive;
+        niters[l] = nit;
+        if (X_out == nullptr || kx < 0) return;
+        gemv<T>(c, n, kx + 1, V, ldv, Yd[kx & 1] + (size_t)l * ldy, x, 0);      // :37-38  x = V_k y
+        stage_out_n<T>(c, X_out + (size_t)l * n, x, n, false, po);
+    };
+    int k = 0;
+    bool unassigned = false;
+    for (k = 0; k < maxit && nactive > 0; ++k) {
+        T* qk = Q + (int64_t)k * ldq;
+        T* v = Q + (int64_t)(k + 1) * ldq;
+        const T* src = nullptr;                                  // the vector the sweep orthogonalises
+        // ---- operator (*_bounds.m:25) ----
+        if (nspace) {
+            T* Aq = AQ + (int64_t)k * ldaq;
+            apply_A<T>(c, A, qk, Aq, EPI_NONE, T(0), nullptr);
+            apply_B<T>(c, B, Aq, v, EPI_NONE, T(0), nullptr);
+        } else {
+            T* Bq = BQ + (int64_t)k * ldbq;
+            T* w = ABQ + (int64_t)k * ldaq;
+            if (fplan) {
+                fused_ab(c, B, fplan, qk, Bq, w);
+            } else {
+                apply_B<T>(c, B, qk, Bq, EPI_NONE, T(0), nullptr);
+                apply_A<T>(c, A, Bq, w, EPI_NONE, T(0), nullptr);
+            }
+            if (orth == HGM_CGS2)
+                HGM_HIP(hipMemcpyAsync(v, w, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+            else src = w;
+        }
+        // ---- orthogonalisation (:26-32) ----
+        T* Hcol = Hd + (int64_t)k * (maxit + 1);
+        if (orth == HGM_CGS2) cgs2<T>(c, dim, Q, ldq, k, Hcol, false);
+        else mgs<T>(c, dim, Q, ldq, k, Hcol, false, src);
+        Reader rd(c);
+        rd.add(&Hh(0, k), Hcol, sizeof(T) * (k + 2));
+        rd.go();
+        if (Hh(k + 1, k) == 0) {                                 // :31  breakdown: every lambda stops here
+            if (k == 0) unassigned = true;
+            for (int l = 0; l < nlam; ++l)
+                if (active[l]) {
+                    // the single solver's convention: niters = k + 1, history entry k stays 0, x is
+                    // the previous iterate
+                    if (err_surf) err_surf[(size_t)l * maxit + k] = 0.0;
+                    if (res_surf) res_surf[(size_t)l * maxit + k] = 0.0;
+                    if (sol_surf) sol_surf[(size_t)l * maxit + k] = 0.0;
+                    finish(l, k + 1, k - 1);
+                }
+            ++k;
+            break;
+        }
+        // ---- projected solves (:34-36), one per running lambda; Hk'*Hk and Hk'*tk are shared ----
+        const int kk = k + 1;
+        G.assign((size_t)kk * kk, 0.0);
+        for (int i = 0; i < kk; ++i)
+            for (int j = 0; j < kk; ++j) {
+                double s = 0;
+                for (int r = 0; r <= kk; ++r) s += Hh(r, i) * Hh(r, j);
+                G[(size_t)j * kk + i] = s;
+            }
+        rhs.assign(kk, 0.0);
+        for (int i = 0; i < kk; ++i) rhs[i] = Hh(0, i) * beta;
+        y.assign(kk, 0.0);
+        std::fill(Yh.begin(), Yh.end(), 0.0);
+        for (int l = 0; l < nlam; ++l) {
+            if (!active[l]) continue;
+            M = G;
+            for (int i = 0; i < kk; ++i) M[(size_t)i * kk + i] = G[(size_t)i * kk + i] + lambdas[l];
+            dense::mldivide_square(kk, M.data(), rhs.data(), y.data());
+            std::memcpy(&Yh[(size_t)l * ldy], y.data(), sizeof(double) * kk);
+        }
+        T* Yk = Yd[k & 1];
+        h2d(c, Yk, Yh.data(), sizeof(T) * Yh.size());
+        // ---- monitors of every lambda (:37-41): two passes over the kept products ----
+        proj_norms<T>(c, m, kk, W, ldaq, Yk, ldy, nlam, b, mon, mon + nlam);
+        proj_norms<T>(c, n, kk, V, ldv, Yk, ldy, nlam, xt, mon + 2 * nlam, mon + 3 * nlam);
+        Reader rm(c);
+        rm.add(mh.data(), mon, sizeof(T) * 4 * nlam);
+        rm.go();
+        for (int l = 0; l < nlam; ++l) {
+            if (!active[l]) continue;
+            const double res = std::sqrt(mh[l]) / nb;
+            if (res_surf) res_surf[(size_t)l * maxit + k] = res;
+            if (err_surf && xt) err_surf[(size_t)l * maxit + k] = std::sqrt(mh[2 * (size_t)nlam + l]) / nxt;
+            if (sol_surf) sol_surf[(size_t)l * maxit + k] = std::sqrt(mh[3 * (size_t)nlam + l]);
+            if (res <= tol || kk == maxit) finish(l, kk, k);      // :79-83
+        }
+    }
+    if (ksteps) *ksteps = k;
+    if (o && o->H_out) std::memcpy(o->H_out, H.data(), sizeof(double) * H.size());
+    if (unassigned)
+        throw Error{HGM_E_NOT_ASSIGNED, "Output argument \"x\" not assigned during call (breakdown at k = 1)"};
+    return HGM_OK;
+}
+
 // explicit instantiations used by capi.cpp
 template int lsqr_t<double>(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*, const double*,
                             double, int, bool, double, double*, double*, double*, int*);

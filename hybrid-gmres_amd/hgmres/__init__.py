@@ -6,6 +6,7 @@ The compute path is ``libhgmres.so`` (hand-written HIP for gfx950, C ABI in
 interface plus the synthetic 2-D tomography problem generator.
 """
 from .core import spmv_ab, fused_plan_info  # noqa: F401
+from .core import SweepResult, gmres_lambda_sweep, proj_norms  # noqa: F401
 from .core import (  # noqa: F401
     ABgmres_hybrid_bounds,
     ABgmres_nonhybrid_bounds,
@@ -42,5 +43,5 @@ __all__ = [
     "gcv_fminbnd", "ABgmres_hybrid_bounds", "ABgmres_nonhybrid_bounds",
     "BAgmres_hybrid_bounds", "BAgmres_nonhybrid_bounds", "Context", "SparseOperator",
     "as_operator", "default_context", "HgmError", "OutputNotAssigned", "problems", "regtools", "analysis",
-    "eig", "filter_factors", "ritz",
+    "eig", "filter_factors", "ritz", "gmres_lambda_sweep", "proj_norms", "SweepResult",
 ]

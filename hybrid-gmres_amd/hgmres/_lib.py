@@ -85,6 +85,8 @@ _SIGS = {
     "hgm_mat_destroy": (None, [c_void_p]),
     "hgm_spmv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgm_spmv_ab": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hgm_proj_norms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp, dp]),
+    "hgm_proj_norms_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp]),
     "hgm_fused_plan_info": (c_int, [c_void_p, c_void_p, c_void_p, dp, P(C.c_uint64), ip64, P(c_int)]),
     "hgm_dev_alloc": (c_int, [c_void_p, c_int64, P(c_void_p)]),
     "hgm_dev_free": (c_int, [c_void_p, c_void_p]),
@@ -100,6 +102,8 @@ _SIGS = {
     "hgm_hybrid_ab_gmres_rtp_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, c_double, dp, dp, dp, P(c_int)]),
     "hgm_hybrid_ba_gmres_rtp_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, c_double, dp, dp, dp, P(c_int)]),
     "hgm_gmres_bounds_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, c_double, c_int, c_int, dp, dp, dp, P(c_int)]),
+    "hgm_gmres_bounds_sweep": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, c_int, c_int,
+                                       dp, dp, dp, dp, P(c_int), P(c_int)]),
     "hgm_lsqr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, P(c_int)]),
     "hgm_lsmr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, dp, P(c_int)]),
     "hgm_arnoldi": (c_int, [c_void_p, c_void_p, c_void_p, dp, c_int, c_int, c_double, c_int, dp, dp, P(c_int)]),

@@ -53,11 +53,16 @@ def regularization_problem(n: int = 32, problem: str = "shaw", noise_level: floa
 
 
 def analyze_regularization(P: RegularizationProblem, *, maxit: int = 32, tol: float = 1e-6,
-                           lambda_range=None, k_gcv: int = 20, ctx=None, DeltaM_factored: bool = False) -> dict:
+                           lambda_range=None, k_gcv: int = 20, ctx=None, DeltaM_factored: bool = False,
+                           sweep: bool = False) -> dict:
     """Numeric outputs of ``analyze_regularization.m`` (no figures).
 
     ``DeltaM_factored``: pass DeltaM as the factor pair (A, E) / (E, A) instead of the
-    formed product (the at-scale form; the bounds outputs used here do not depend on it)."""
+    formed product (the at-scale form; the bounds outputs used here do not depend on it).
+
+    ``sweep``: take the six arrays of the lambda loop (``:22-33``) from two
+    :func:`hgmres.core.gmres_lambda_sweep` calls, one Arnoldi per side instead of one solve per
+    lambda and side (fp64 operators, single rank, not in parity mode)."""
     ctx = ctx or core.default_context()
     lam_range = np.logspace(-10, 0, 100) if lambda_range is None else np.asarray(lambda_range, dtype=np.float64)
     A = core.as_operator(P.A, ctx)                             # uploaded once, reused by every solve
@@ -67,7 +72,13 @@ def analyze_regularization(P: RegularizationProblem, *, maxit: int = 32, tol: fl
     nb = np.linalg.norm(P.b)
     out = {k: np.zeros(lam_range.size) for k in
            ("res_norms_ab", "sol_norms_ab", "err_norms_ab", "res_norms_ba", "sol_norms_ba", "err_norms_ba")}
-    for i, lam in enumerate(lam_range):                        # :22-33
+    if sweep:                                                  # :22-33 from one Arnoldi per side
+        for side in ("ab", "ba"):
+            S = core.gmres_lambda_sweep(A, Bp, P.b, P.x_true, tol, maxit, lam_range, side, ctx=ctx, return_x=True)
+            out[f"res_norms_{side}"] = np.linalg.norm(P.b[:, None] - P.A @ S.X, axis=0) / nb   # :25 / :30
+            out[f"sol_norms_{side}"] = np.linalg.norm(S.X, axis=0)                            # :26 / :31
+            out[f"err_norms_{side}"] = S.err[S.niters - 1, np.arange(lam_range.size)]         # :27 / :32
+    for i, lam in enumerate(lam_range if not sweep else ()):   # :22-33
         x_ab, err_ab = core.ABgmres_hybrid_bounds(A, Bp, P.b, P.x_true, tol, maxit, lam, ctx=ctx)[:2]   # :24
         out["res_norms_ab"][i] = np.linalg.norm(P.b - P.A @ x_ab) / nb                                  # :25
         out["sol_norms_ab"][i] = np.linalg.norm(x_ab)                                                   # :26
@@ -95,4 +106,24 @@ def analyze_regularization(P: RegularizationProblem, *, maxit: int = 32, tol: fl
     out["solution_nonhybrid_ba"] = core.BAgmres_nonhybrid_bounds(A, Bp, P.b, P.x_true, tol, maxit, dm_ba,
                                                                  ctx=ctx)[0]     # :123
     out["lambda_range"] = lam_range
+    return out
+
+
+def error_surface(A, B, b, x_true, lambdas, maxit, tol=1e-10, *, ctx=None) -> dict:
+    """The numeric part of ``plot_error_surface.m:21-48``: the (k, lambda) error surfaces of
+    ``ABgmres_hybrid_bounds`` and ``BAgmres_hybrid_bounds`` (``maxit x nlam``: the transpose of the
+    reference's arrays; NaN past each lambda's stopping iteration, ``:32,36``) and the optimal point of
+    each (``:45-48``, ``:69-72``: ``k`` 1-based, ``lambda``, ``error``; ties go to the smaller k, then the
+    smaller lambda index, as MATLAB's ``min`` over the flattened array), from one Arnoldi per side
+    (:func:`hgmres.core.gmres_lambda_sweep`) instead of one solve per lambda and side (``:28-42``)."""
+    lam = np.asarray(lambdas, dtype=np.float64).reshape(-1)
+    out = {"lambdas": lam, "iterations": np.arange(1, int(maxit) + 1)}
+    for side in ("ab", "ba"):
+        S = core.gmres_lambda_sweep(A, B, b, x_true, tol, maxit, lam, side, ctx=ctx)
+        surf = S.err
+        out[f"error_surface_{side}"] = surf
+        out[f"residual_surface_{side}"] = S.res
+        out[f"niters_{side}"] = S.niters
+        k, l = np.unravel_index(int(np.nanargmin(surf)), surf.shape)     # :45-46
+        out[f"optimal_{side}"] = {"k": int(k) + 1, "lambda": float(lam[l]), "error": float(surf[k, l])}
     return out

@@ -613,6 +613,103 @@ def BAgmres_nonhybrid_bounds(A, B, b, x_true, tol, maxit, DeltaM=None, *, ctx=No
                    DeltaM=DeltaM, ritz_steps=ritz_steps, return_ritz=return_ritz)
 
 
+class SweepResult:
+    """Outputs of :func:`gmres_lambda_sweep`.  ``err``, ``res``, ``sol``: ``maxit x nlam`` surfaces
+    (row k-1 = iteration k, column l = ``lambdas[l]``; NaN past ``niters[l]``); ``niters``: per lambda;
+    ``X`` (``n x nlam``) and ``H`` when requested, else None; ``ksteps``: Arnoldi steps performed."""
+
+    def __init__(self, lambdas, err, res, sol, niters, X, H, ksteps):
+        self.lambdas, self.err, self.res, self.sol = lambdas, err, res, sol
+        self.niters, self.X, self.H, self.ksteps = niters, X, H, ksteps
+
+
+def _side(side):
+    if side in (L.HGM_SIDE_AB, L.HGM_SIDE_BA) and not isinstance(side, str):
+        return int(side)
+    s = str(side).lower()
+    if s not in ("ab", "ba"):
+        raise ValueError(f"side must be 'ab' or 'ba', not {side!r}")
+    return L.HGM_SIDE_AB if s == "ab" else L.HGM_SIDE_BA
+
+
+def gmres_lambda_sweep(A, B, b, x_true, tol, maxit, lambdas, side, *, ctx=None, orth="mgs", return_x=False,
+                       return_H=False):
+    """``ABgmres_hybrid_bounds`` / ``BAgmres_hybrid_bounds`` (``side`` 'ab' / 'ba') for every lambda of
+    ``lambdas`` from ONE Arnoldi (``hgm_gmres_bounds_sweep``): lambda enters only the projected solve
+    ``yk = (Hk'*Hk + lambda*eye(k)) \\ (Hk'*tk)`` (``*_hybrid_bounds.m:34-36``).  Column l of the result's
+    surfaces is the history of the single solve at ``lambdas[l]``; ``sol`` adds ``||x_k||`` (the L-curve).
+    ``x_true`` may be None (``err`` stays NaN)."""
+    ctx, Ao, Bo = _ops(A, B, ctx)
+    m, n = Ao.shape
+    maxit = int(maxit)
+    b = _f64(b, m, "b")
+    xt = _f64(x_true, n, "x_true") if x_true is not None else None
+    lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+    nl = lam.size
+    err, res, sol = (np.full(maxit * max(nl, 1), np.nan) for _ in range(3))
+    X = np.zeros(n * max(nl, 1)) if return_x else None
+    nit = np.zeros(max(nl, 1), dtype=np.int32)
+    ks = C.c_int(0)
+    H = np.zeros((maxit + 1) * maxit) if return_H else None
+    o = _opts(orth, H)
+    _check(L.load().hgm_gmres_bounds_sweep(ctx.handle, C.byref(o), Ao._h, Bo._h, _dp(b), _dp(xt), float(tol), maxit,
+                                           _dp(lam), int(nl), _side(side), _dp(X), _dp(err), _dp(res), _dp(sol),
+                                           nit.ctypes.data_as(C.POINTER(C.c_int)), C.byref(ks)), ctx)
+    shp = (nl, maxit)
+    return SweepResult(lam, err.reshape(shp).T.copy(), res.reshape(shp).T.copy(), sol.reshape(shp).T.copy(),
+                       nit.astype(int), X.reshape(nl, n).T.copy() if return_x else None,
+                       H.reshape(maxit, maxit + 1).T.copy() if return_H else None, ks.value)
+
+
+def proj_norms(V, Y, t=None, *, ctx=None, loop=False):
+    """``(d, s)`` with ``d[l] = ||V @ Y[:, l] - t||^2`` and ``s[l] = ||V @ Y[:, l]||^2`` from the device
+    primitive ``hgm_proj_norms`` (one pass over V, the product never stored).  ``V`` is used as given when
+    it is Fortran-ordered, so a column-major view with a leading dimension larger than its row count
+    (``buf[:rows, :]`` of an ``ld x k`` array) is passed with that leading dimension.
+    ``loop``: the yardstick ``hgm_proj_norms_loop`` instead (the solvers' single-coefficient monitor, one
+    launch per column; ``t`` required, even leading dimension); returns ``(d, None)``."""
+    V = np.asarray(V, dtype=np.float64)
+    Y = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+    if V.ndim != 2 or Y.ndim != 2 or Y.shape[0] != V.shape[1]:
+        raise ValueError("proj_norms: V is rows x k and Y is k x L")
+    rows, k = V.shape
+    nl = Y.shape[1]
+    if rows < 1 or k < 1 or nl < 1:
+        raise ValueError("proj_norms: rows, k and L must be >= 1")
+    ctx = ctx or default_context()
+    lib = L.load()
+    es = V.itemsize
+    if not (V.strides[0] == es and (k == 1 or (V.strides[1] % es == 0 and V.strides[1] >= rows * es))):
+        V = np.asfortranarray(V)
+    ldv = rows if k == 1 else V.strides[1] // es
+    # the whole leading-dimension span is uploaded (padding rows included), except past the last column
+    nv = ldv * (k - 1) + rows
+    vflat = np.lib.stride_tricks.as_strided(V, shape=(nv,), strides=(es,)) if ldv != rows else V.reshape(-1, order="F")
+    vflat = np.ascontiguousarray(vflat)
+    tt = _f64(t, rows, "t") if t is not None else None
+    ptr = [C.c_void_p() for _ in range(3)]
+    d, s = np.zeros(nl), np.zeros(nl)
+    try:
+        for p_, cnt in zip(ptr, (nv, k * nl, rows)):
+            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, cnt), C.byref(p_)), ctx)
+        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], vflat.ctypes.data_as(C.c_void_p), 8 * nv), ctx)
+        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[1], Y.ctypes.data_as(C.c_void_p), 8 * k * nl), ctx)
+        if tt is not None:
+            _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[2], tt.ctypes.data_as(C.c_void_p), 8 * rows), ctx)
+        if loop:
+            _check(lib.hgm_proj_norms_loop(ctx.handle, rows, k, ptr[0], ldv, ptr[1], k, nl,
+                                           ptr[2] if tt is not None else None, _dp(d)), ctx)
+            s = None
+        else:
+            _check(lib.hgm_proj_norms(ctx.handle, rows, k, ptr[0], ldv, ptr[1], k, nl,
+                                      ptr[2] if tt is not None else None, _dp(d), _dp(s)), ctx)
+    finally:
+        for p_ in ptr:
+            if p_.value:
+                lib.hgm_dev_free(ctx.handle, p_)
+    return d, s
+
+
 def _gkb_ops(A, ctx, At=None, dtype=L.HGM_F64):
     ctx = ctx or (A.ctx if isinstance(A, SparseOperator) else default_context())
     Ao = as_operator(A, ctx, dtype)

@@ -19,6 +19,8 @@
  *   hgm_gcv_function         <- gcv_function.m:1          gcv_val
  *   hgm_arnoldi / hgm_gcv_from_H  <- gcv_function.m:18-33 / :35-58 split (Arnoldi once, lambda on H;
  *                               pattern of plot_gcv_surface.m:58-122)
+ *   hgm_gmres_bounds_sweep   <- the lambda loops of analyze_regularization.m:22-33 / plot_error_surface.m:28-42
+ *                               over *_hybrid_bounds.m (one Arnoldi for every lambda)
  *   hgm_gmres_bounds_filter  <- outputs 5-8 of the four *_bounds.m (phi/dphi filter-factor bounds,
  *                               eig(M) of :4-9 replaced by device Ritz pairs)
  *   hgm_mat_create_csc       <- MATLAB sparse (CSC, jc/ir/pr) operand hand-over
@@ -305,6 +307,22 @@ HGM_API int hgm_spmv(hgm_ctx* ctx, const hgm_mat* A, const void* x_dev, void* y_
  * in the reference pixel order, as hgm_spmv's. */
 HGM_API int hgm_spmv_ab(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, const void* q_dev, void* Bq_dev,
                         void* ABq_dev);
+/* Multi-coefficient projected norms (the monitors of hgm_gmres_bounds_sweep), on device pointers:
+ * V is rows x k column-major with leading dimension ldv >= rows, Y is k x nlam column-major (ldy >= k),
+ * t has rows entries (NULL: zeros).  For every column l, in ONE pass over V (the rows x nlam product is
+ * never stored; fp64 matrix cores):
+ *     sumsq_diff[l] = sum_i ((V*Y)(i,l) - t(i))^2        sumsq[l] (optional) = sum_i (V*Y)(i,l)^2
+ * written to host buffers.  Fixed summation order (two calls give the same bits).  k <= 256. */
+HGM_API int hgm_proj_norms(hgm_ctx* ctx, int64_t rows, int k, const double* V_dev, int64_t ldv,
+                           const double* Y_dev, int64_t ldy, int nlam, const double* t_dev,
+                           double* sumsq_diff_host, double* sumsq_host);
+/* The same sumsq_diff from the solvers' own single-coefficient monitor (the residual-only form of the
+ * GMRES reconstruction launch), one launch pair per column of Y: V is read nlam times.  The yardstick
+ * hgm_proj_norms is measured against (scripts/sweep_micro.py) and a cross-check of it.  t is required,
+ * ldv must be even. */
+HGM_API int hgm_proj_norms_loop(hgm_ctx* ctx, int64_t rows, int k, const double* V_dev, int64_t ldv,
+                                const double* Y_dev, int64_t ldy, int nlam, const double* t_dev,
+                                double* sumsq_diff_host);
 /* The one-pass plan of the pair (A, B) under the context's current options, built if it is not
  * yet: the seconds its build took, a 64-bit FNV-1a checksum over every plan array (so two builds
  * can be compared byte for byte), the partial slots, and whether the device built the ray sets
@@ -362,6 +380,23 @@ HGM_API int hgm_gmres_bounds_ex(hgm_ctx* ctx, const hgm_opts* opts, const hgm_ma
                                 const hgm_mat* B, const double* b, const double* x_true, double tol,
                                 int maxit, double lambda, int side, int hybrid, double* x,
                                 double* error_norm, double* residual_norm, int* niters);
+/* Lambda sweep of the hybrid PTR solvers (ABgmres_hybrid_bounds.m / BAgmres_hybrid_bounds.m; the loops of
+ * analyze_regularization.m:22-33 and plot_error_surface.m:28-42): lambda enters only the projected
+ * solve (:34-36), so ONE Arnoldi serves every lambda.  Column l of every output is what
+ * hgm_gmres_bounds_ex(lambda = lambdas[l], side, hybrid = 1) returns: niters[l], the first niters[l]
+ * entries of column l of error_surf / residual_surf (each maxit x nlam column-major; entries past
+ * niters[l] are NaN) and X(:,l) (optional, n x nlam column-major) at that lambda's own stopping
+ * iteration; solnorm_surf (optional) is ||x_k||, the L-curve's second axis.  x_true may be NULL
+ * (error_surf stays NaN).  *ksteps (optional): Arnoldi steps performed (the sweep ends when no lambda
+ * is running).  opts: orth and H_out are honoured.  A breakdown follows the single solver
+ * (HGM_E_NOT_ASSIGNED at k = 1).  Refused: HGM_E_ARG for fp32 operators, parity mode, HGM_DEVICE_PTRS,
+ * nlam < 1, a negative or non-finite lambda; HGM_E_UNSUPPORTED on a communicator or a context with a
+ * host all-reduce hook (single rank only). */
+HGM_API int hgm_gmres_bounds_sweep(hgm_ctx* ctx, const hgm_opts* opts, const hgm_mat* A, const hgm_mat* B,
+                                   const double* b, const double* x_true, double tol, int maxit,
+                                   const double* lambdas, int nlam, int side, double* X,
+                                   double* error_surf, double* residual_surf, double* solnorm_surf,
+                                   int* niters, int* ksteps);
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* ctx, const hgm_opts* opts, const hgm_mat* A,
                                const hgm_mat* At, const double* b, const double* x_true, double tol,
                                int maxit, double* x, double* error_norm, double* residual_norm,
@@ -421,7 +456,8 @@ HGM_API int hgm_eig(int n, const double* A, double* wr, double* wi, double* V);
 /* ---- timing hooks used by bench.py ---------------------------------------- */
 /* Average device time (ms) of the named kernel class over the calls since the
  * last reset, measured with HIP events on the context stream.  classes:
- * 0 = SpMV on A (ray-major), 1 = SpMV on B/Aᵀ (pixel-major), 2 = MGS pass.
+ * 0 = SpMV on A (ray-major), 1 = SpMV on B/Aᵀ (pixel-major), 2 = MGS pass, 3 = the one-pass A*(B*q),
+ * 4 = the launches of a hgm_proj_norms / hgm_proj_norms_loop call.
  * enable: 0 = off, 1 = every class, HGM_TIMING_CLASSES(mask) = only the classes whose
  * bit is set (each timed launch carries events, so time only what is read). */
 #define HGM_TIMING_CLASSES(mask) (0x100 | (mask))

@@ -18,6 +18,11 @@
  *   hgmres_mex('gcv_fminbnd', H,beta,trace_m,lo,hi,tolx) -> [lambda, gcv]   analyze_regularization.m:37-46
  *   hgmres_mex('gmres_bounds', side,hybrid, A,B,b,x_true,tol,maxit,lambda, DeltaM[, DeltaR[, ritz_steps]])
  *        -> [x,err,res,niters,phi_final,dphi_final,phi_iter,dphi_iter]   {AB,BA}gmres_{hybrid,nonhybrid}_bounds.m:1-2
+ *   hgmres_mex('gmres_lambda_sweep', side, A,B,b,x_true,tol,maxit,lambdas)
+ *        -> [error_surf, residual_surf, solnorm_surf, niters, X]   the lambda loops of analyze_regularization.m:22-33 /
+ *        plot_error_surface.m:28-42 over {AB,BA}gmres_hybrid_bounds from ONE Arnoldi (hgm_gmres_bounds_sweep):
+ *        maxit x nlam surfaces (NaN past niters(l)), X n x nlam; x_true may be [] (error_surf NaN).  The sweep
+ *        runs the production kernels whatever the 'parity' setting (it has no fixed-order form).
  *   hgmres_mex('device', d)                      select the HIP device (default 0)
  *   hgmres_mex('parity', 'auto'|'on'|'off')      summation orders (below; default 'auto')
  *
@@ -416,6 +421,42 @@ static void bounds(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(k);
 }
 
+/* [error_surf, residual_surf, solnorm_surf, niters, X] = hgmres_mex('gmres_lambda_sweep', side, A, B, b, x_true,
+ * tol, maxit, lambdas) */
+static void lambda_sweep(int nlhs, mxArray* plhs[], const mxArray* prhs[]) {
+    const int side = side_of(prhs[1]);
+    need_double(prhs[8], "lambdas");
+    const int64_t nl = (int64_t)mxGetNumberOfElements(prhs[8]);
+    if (mxIsSparse(prhs[8]) || nl < 1 || nl > 2147483647) fail("hgmres:arg", "hgmres: lambdas must be a dense non-empty vector");
+    const double* lam = mxGetDoubles(prhs[8]);
+    for (int64_t l = 0; l < nl; ++l)
+        if (!(lam[l] >= 0.0) || !isfinite(lam[l])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
+    hgm_mat* A = op(prhs[2], "A");
+    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
+    hgm_mat* B = op(prhs[3], "B");
+    int64_t m = 0, n = 0;
+    hgm_mat_info(A, &m, &n, NULL, NULL);
+    const double* b = vec(prhs[4], m, "b", 0);
+    const double* xt = vec(prhs[5], n, "x_true", 1);
+    const double tol = scalar(prhs[6], "tol");
+    const int maxit = maxit_of(prhs[7]);
+    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nl, mxREAL);
+    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nl, mxREAL);
+    mxArray* sn = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nl, mxREAL);
+    mxArray* X = nlhs > 4 ? mxCreateDoubleMatrix((mwSize)n, (mwSize)nl, mxREAL) : NULL;
+    int* nit = (int*)mxCalloc((size_t)nl, sizeof(int));
+    check(hgm_gmres_bounds_sweep(ctx(), NULL, A, B, b, xt, tol, maxit, lam, (int)nl, side, X ? mxGetDoubles(X) : NULL,
+                                 mxGetDoubles(e), mxGetDoubles(r), mxGetDoubles(sn), nit, NULL));
+    mxArray* ni = mxCreateDoubleMatrix((mwSize)nl, 1, mxREAL);
+    for (int64_t l = 0; l < nl; ++l) mxGetDoubles(ni)[l] = (double)nit[l];
+    mxFree(nit);
+    plhs[0] = e;
+    if (nlhs > 1) plhs[1] = r;
+    if (nlhs > 2) plhs[2] = sn;
+    if (nlhs > 3) plhs[3] = ni;
+    if (nlhs > 4) plhs[4] = X;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char fn[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], fn, sizeof fn) != 0)
@@ -447,6 +488,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(fn, "gmres_bounds")) {
         nargs(nrhs, 9, 12, fn);
         bounds(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(fn, "gmres_lambda_sweep")) {
+        nargs(nrhs, 8, 8, fn);
+        lambda_sweep(nlhs, plhs, prhs);
     } else if (!strcmp(fn, "parity")) {
         nargs(nrhs, 1, 1, fn);
         char mode[8];
