@@ -44,6 +44,10 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                        const double* xt_in, double tol, int maxit, const double* lambdas, int nlam, int side,
                        double* X_out, double* err_surf, double* res_surf, double* sol_surf, int* niters,
                        int* ksteps);
+int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
+                       int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
+                       const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
+                       double* res_hist, int* niters, int* col_status);
 // bounds.cpp
 int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
                         const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
@@ -1012,6 +1016,45 @@ HGM_API int hgm_spmv_ab(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const vo
     return HGM_OK;
 }
 
+static void spmm_impl(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, int64_t ldx, double* Y, int64_t ldy) {
+    HGM_HIP(hipSetDevice(c->device));
+    HGM_REQUIRE(A->dtype == HGM_F64, "spmm: fp64 operators only");
+    HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, "spmm: 1 <= nvec <= 8");
+    HGM_REQUIRE(ldx >= A->cols && ldy >= A->rows, "spmm: ldx >= cols and ldy >= rows");
+    const int NV = spmm_width(nvec);
+    const int64_t rows = A->rows, cols = A->cols;
+    double* Xi = c->buf<double>("spmm_xi", (size_t)(cols > 0 ? cols : 1) * NV);
+    double* Yi = c->buf<double>("spmm_yi", (size_t)(rows > 0 ? rows : 1) * NV);
+    // a pixel space stored tiled: the columns are permuted on the way in / out, as hgm_spmv's vector
+    double* xp = A->col_order.trivial() ? nullptr : c->buf<double>("spmm_x_pix", (size_t)cols * nvec);
+    double* yp = A->row_order.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
+    MvCols src, dst;
+    for (int r = 0; r < SPMM_MAXV; ++r) src.p[r] = dst.p[r] = nullptr;
+    hipEvent_t tm;
+    timing_begin(c, KC_SPMM, &tm);
+    for (int r = 0; r < nvec; ++r) {
+        src.p[r] = const_cast<double*>(X) + r * ldx;
+        if (xp) {
+            pix_permute<double>(c, A->col_order, X + r * ldx, xp + (size_t)r * cols, 0);
+            src.p[r] = xp + (size_t)r * cols;
+        }
+        dst.p[r] = yp ? yp + (size_t)r * rows : Y + r * ldy;
+    }
+    mv_pack(c, cols, nvec, src, Xi);
+    spmm(c, A, nvec, Xi, Yi);
+    mv_unpack(c, rows, nvec, Yi, dst);
+    if (yp)
+        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, A->row_order, yp + (size_t)r * rows, Y + r * ldy, 1);
+    // the operator's entries once, the interleaved vectors once each way, the columns once each way
+    timing_end(c, KC_SPMM, tm, 12.0 * (double)A->nnz + 8.0 * (rows + 1) + 8.0 * (2.0 * NV + nvec) * (rows + cols));
+}
+
+HGM_API int hgm_spmm(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, int64_t ldx, double* Y, int64_t ldy) {
+    if (!c || !A || !X || !Y) return HGM_E_ARG;
+    HGM_TRY(c, spmm_impl(c, A, nvec, X, ldx, Y, ldy));
+    return HGM_OK;
+}
+
 HGM_API int hgm_proj_norms(hgm_ctx* c, int64_t rows, int k, const double* V, int64_t ldv, const double* Y,
                            int64_t ldy, int nlam, const double* t, double* sumsq_diff, double* sumsq) {
     if (!c || !V || !Y || !sumsq_diff) return HGM_E_ARG;
@@ -1135,6 +1178,14 @@ HGM_API int hgm_gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat*
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
     HGM_SOLVE(c, gmres_bounds_sweep(c, o, A, B, b, xt, tol, maxit, lambdas, nlam, side, X, err, res, sol, niters,
                                     ksteps));
+}
+HGM_API int hgm_gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
+                                   int64_t ldb, int nrhs, const double* xt, int64_t ldxt, double tol, int maxit,
+                                   const double* lambdas, int side, int hybrid, double* X, int64_t ldx, double* err,
+                                   double* res, int* niters, int* col_status) {
+    if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
+    HGM_SOLVE(c, gmres_bounds_batch(c, o, A, B, Bm, ldb, nrhs, xt, ldxt, tol, maxit, lambdas, side, hybrid ? 1 : 0, X,
+                                    ldx, err, res, niters, col_status));
 }
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b,
                                const double* xt, double tol, int maxit, double* x, double* err, double* res,

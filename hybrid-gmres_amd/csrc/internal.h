@@ -56,14 +56,14 @@ struct DevBuf {
 };
 
 // Kernel classes timed by hgm_kernel_timing (bench roofline).
-enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_N = 5 };
+enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_SPMM = 5, KC_N = 6 };
 
 struct Timing {
     bool on = false;
     bool paused = false;   // hgm_kernel_timing_pause: armed but not recording
     unsigned mask = 0xffu;   // timed classes
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[KC_N];
-    double bytes[KC_N] = {0, 0, 0, 0, 0};
+    double bytes[KC_N] = {0, 0, 0, 0, 0, 0};
     std::vector<hipEvent_t> pool;
     hipEvent_t get();
     void clear();
@@ -349,6 +349,21 @@ void recon(hgm_ctx* c, int64_t n, int k, const T* Q, int64_t ldq, const T* y, T*
 template <typename T>
 void proj_norms(hgm_ctx* c, int64_t rows, int k, const T* V, int64_t ldv, const T* Y, int64_t ldy, int L,
                 const T* t, T* d_out, T* s_out);
+
+// Multi-vector products (spmm.hip; hgm_spmm and the operator of hgm_gmres_bounds_batch).  An interleaved
+// multi-vector of width NV = spmm_width(nvec) in {1, 2, 4, 8} stores element (i, r) at Xi[i*NV + r];
+// slots nvec..NV-1 hold zeros.  spmm: Yi = M Xi with the operator's entries read once for all slots, in
+// M's stored index orders; a slot's bits depend on the row and M->group only (not on nvec, the slot or
+// the other slots).  mv_pack / mv_unpack convert from / to nvec column-major vectors given as a pointer
+// table (last: the launch carries the armed timing stop event, device_common.h launch()).
+constexpr int SPMM_MAXV = 8;
+struct MvCols {
+    double* p[SPMM_MAXV];
+};
+int spmm_width(int nvec);
+void mv_pack(hgm_ctx* c, int64_t n, int nvec, const MvCols& src, double* Xi);
+void mv_unpack(hgm_ctx* c, int64_t n, int nvec, const double* Yi, const MvCols& dst, bool last = false);
+void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi);
 
 // MGS sweep of v = Q(:,kk+1) against Q(:,0..kk); writes Hcol[0..kk+1] (device) and
 // normalises Q(:,kk+1) unless H(kk+1,kk) == 0.  dist: n-vectors sharded (scalar all-reduce

@@ -9,6 +9,7 @@
 // (A_g = A(:,P_g), B_g = B(P_g,:)); every `A*v` is followed by an all-reduce of the
 // m-vector, every inner product of n-vectors by a scalar all-reduce; m-vectors
 // (b, u, the AB-side Krylov basis, A*Q columns) are replicated.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1840,6 +1841,284 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     if (o && o->H_out) std::memcpy(o->H_out, H.data(), sizeof(double) * H.size());
     if (unassigned)
         throw Error{HGM_E_NOT_ASSIGNED, "Output argument \"x\" not assigned during call (breakdown at k = 1)"};
+    return HGM_OK;
+}
+
+// ============================================================================
+// Batched *_bounds solves: nrhs right-hand sides against one operator pair in lockstep
+// ============================================================================
+// plot_error_vs_noise_level.m:28-54 runs the four *_bounds solvers for every noise level on the same
+// A and B: each of those solves streams the operators from HBM once per iteration.  Here the columns
+// advance together and iteration k's operator is two multi-vector passes (spmm.hip) over the packed
+// q_k of the columns still running, so the operators' entries are read once per group of up to 8
+// columns.  Everything else is the single solver's, per column: one Krylov basis each (one slab, the
+// k-th vectors a constant stride apart), mgs / cgs2, the host projected solve (*_bounds.m:34-36), the
+// monitors from the kept products (:37-41, recon).  Column j of every output is what
+// hgm_gmres_bounds_ex(b = Bm(:,j), x_true = XT(:,j), lambda = lambdas[j]) returns, with its own
+// stopping iteration and breakdown convention; a finished column leaves the batch and the later
+// passes are repacked over the rest.  The multi-vector product's bits do not depend on the group a
+// column is packed into, and every other kernel runs per column with scratch of its own, so a
+// column's bits do not depend on its neighbours (which is why even one column takes the spmm route
+// and never the one-pass plan).
+int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
+                       int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
+                       const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
+                       double* res_hist, int* niters, int* col_status) {
+    check_dims(A, B);
+    solver_guard(c);
+    HGM_REQUIRE(B != nullptr, "B is NULL");
+    HGM_REQUIRE(A->dtype == HGM_F64, "batched solve: fp64 operators only");
+    if (dist_n(c) || c->host_ar != nullptr)
+        throw Error{HGM_E_UNSUPPORTED, "batched solve: single rank only (no communicator / all-reduce hook)"};
+    HGM_REQUIRE(!c->num.parity, "batched solve: not in parity mode");
+    HGM_REQUIRE(!(o && (o->flags & HGM_DEVICE_PTRS)), "batched solve: host buffers only (HGM_DEVICE_PTRS refused)");
+    HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, "batched solve: 1 <= nrhs <= 64");
+    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+    HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
+    const int64_t m = A->rows, n = A->cols;
+    HGM_REQUIRE(ldb >= m, "batched solve: ldb >= rows(A)");
+    HGM_REQUIRE(X_out == nullptr || ldx >= n, "batched solve: ldx >= cols(A)");
+    HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, "batched solve: ldxt is 0 (one shared x_true) or >= cols(A)");
+    if (hybrid) {
+        HGM_REQUIRE(lambdas != nullptr, "batched solve: lambdas are required with hybrid = 1");
+        for (int j = 0; j < nrhs; ++j)
+            HGM_REQUIRE(std::isfinite(lambdas[j]) && lambdas[j] >= 0.0,
+                        "batched solve: every lambda must be finite and >= 0");
+    }
+    const PixOrder po = n_order(c, A, B);
+    using T = double;
+    const int orth = o ? o->orth : HGM_MGS;
+    const bool nspace = side == HGM_SIDE_BA;
+    const int64_t dim = nspace ? n : m;
+    const int64_t ldq = krylov_ld(c, dim, false);
+    const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
+    const size_t qs = (size_t)ldq * (maxit + 1);            // one column's basis
+    const size_t hs = (size_t)(maxit + 1) * maxit;           // one column's Hessenberg
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (err_hist) std::fill(err_hist, err_hist + (size_t)maxit * nrhs, nan);
+    if (res_hist) std::fill(res_hist, res_hist + (size_t)maxit * nrhs, nan);
+    for (int j = 0; j < nrhs; ++j) niters[j] = 0;
+    if (col_status) std::fill(col_status, col_status + nrhs, (int)HGM_OK);
+
+    // ---- device storage: every per-column array is one slab with a constant column stride ----
+    T* Qall = c->buf<T>("bt_Q", qs * nrhs);
+    if (krylov_padded(c, ldq)) HGM_HIP(hipMemsetAsync(Qall, 0, sizeof(T) * qs * nrhs, c->stream));
+    // kept products: BA: W = A*Q ; AB: V = B*Q and W = A*B*Q  (the sweep's, per column)
+    T* Wall = c->buf<T>("bt_W", (size_t)ldm * maxit * nrhs);
+    T* Vall = nspace ? nullptr : c->buf<T>("bt_V", (size_t)ldn * maxit * nrhs);
+    T* ball = c->buf<T>("bt_b", (size_t)ldm * nrhs);
+    const int nxt_cols = xt_in ? (ldxt == 0 ? 1 : nrhs) : 1;
+    T* xtall = c->buf<T>("bt_xt", (size_t)ldn * nxt_cols);
+    T* xall = c->buf<T>("bt_x", (size_t)ldn * nrhs);
+    T* Hd = c->buf<T>("bt_H", hs * nrhs);
+    T* Yd = c->buf<T>("bt_y", (size_t)maxit * nrhs);
+    T* mon = c->buf<T>("bt_mon", (size_t)2 * nrhs);          // [res^2, err^2] per column
+    T* scal = c->buf<T>("bt_scal", (size_t)3 * nrhs);        // [||b||^2, ||x_true||^2, ||r0||^2] per column
+    // interleaved multi-vectors of the operator passes (two per space: source and product)
+    T* Im[2] = {c->buf<T>("bt_im0", (size_t)(m > 0 ? m : 1) * SPMM_MAXV),
+                c->buf<T>("bt_im1", (size_t)(m > 0 ? m : 1) * SPMM_MAXV)};
+    T* In[2] = {c->buf<T>("bt_in0", (size_t)(n > 0 ? n : 1) * SPMM_MAXV),
+                c->buf<T>("bt_in1", (size_t)(n > 0 ? n : 1) * SPMM_MAXV)};
+    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(T) * hs * nrhs, c->stream));
+    auto Qj = [&](int j) { return Qall + qs * (size_t)j; };
+    auto Wj = [&](int j) { return Wall + (size_t)ldm * maxit * j; };
+    auto Vj = [&](int j) -> const T* { return nspace ? Qj(j) : Vall + (size_t)ldn * maxit * j; };
+    const int64_t ldv = nspace ? ldq : ldn;
+    auto bj = [&](int j) { return ball + (size_t)ldm * j; };
+    auto xtj = [&](int j) -> const T* { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
+    auto xj = [&](int j) { return xall + (size_t)ldn * j; };
+
+    for (int j = 0; j < nrhs; ++j) h2d(c, bj(j), Bm + (size_t)ldb * j, sizeof(T) * m);
+    if (xt_in) {
+        // x_true in the reference order, permuted into the operators' stored pixel order
+        T* tmp = po.trivial() ? nullptr : c->buf<T>("bt_xt_ref", n > 0 ? n : 1);
+        for (int j = 0; j < nxt_cols; ++j) {
+            T* dst = xtall + (size_t)ldn * j;
+            h2d(c, po.trivial() ? dst : tmp, xt_in + (size_t)ldxt * j, sizeof(T) * n);
+            if (!po.trivial()) pix_permute<T>(c, po, tmp, dst, 0);
+        }
+    } else {
+        HGM_HIP(hipMemsetAsync(xtall, 0, sizeof(T) * ldn, c->stream));   // the monitor's operand; errors stay NaN
+    }
+
+    // per-column scratch of the orthogonalisation: the one-reduction MGS keeps its Gram triangle in a
+    // workspace buffer from step to step, so every column gets workspace names of its own
+    struct ColTag {
+        hgm_ctx* c;
+        std::string saved;
+        ColTag(hgm_ctx* cc, int j) : c(cc), saved(cc->ws_tag) { c->ws_tag = "bt" + std::to_string(j) + ":"; }
+        ~ColTag() { c->ws_tag = saved; }
+    };
+    // one operator pass pair over the columns `cols` (at most 8): src(j) -> [mid(j)] -> dst(j)
+    auto operator_pass = [&](const std::vector<int>& cols, size_t g0, int nv, const hgm_mat* first,
+                             const hgm_mat* second, auto src, auto mid, auto dst) {
+        MvCols ts, tm, td;
+        for (int r = 0; r < SPMM_MAXV; ++r) ts.p[r] = tm.p[r] = td.p[r] = nullptr;
+        for (int r = 0; r < nv; ++r) {
+            const int j = cols[g0 + r];
+            ts.p[r] = const_cast<T*>(src(j));
+            tm.p[r] = mid(j);
+            td.p[r] = dst(j);
+        }
+        hipEvent_t tev = nullptr;
+        timing_begin(c, KC_SPMM, &tev);
+        // first: cols(first) -> rows(first) ; second: rows(first) = cols(second) -> rows(second)
+        const bool from_m = first == B;                          // B maps the ray space to the pixel space
+        T* I0 = from_m ? Im[0] : In[0];
+        T* I1 = from_m ? In[0] : Im[0];
+        mv_pack(c, first->cols, nv, ts, I0);
+        spmm(c, first, nv, I0, I1);
+        if (tm.p[0]) mv_unpack(c, first->rows, nv, I1, tm);
+        double bytes = 12.0 * first->nnz + 8.0 * spmm_width(nv) * (first->rows + first->cols);
+        if (second) {
+            T* I2 = from_m ? Im[1] : In[1];
+            spmm(c, second, nv, I1, I2);
+            mv_unpack(c, second->rows, nv, I2, td);
+            bytes += 12.0 * second->nnz + 8.0 * spmm_width(nv) * (second->rows + second->cols);
+        }
+        timing_end(c, KC_SPMM, tev, bytes);
+    };
+
+    // ---- r0 (*_bounds.m:11-13): BA: B*(b - A*0) ; AB: b - A*(B*0) ----
+    std::vector<int> act(nrhs);
+    for (int j = 0; j < nrhs; ++j) act[j] = j;
+    if (nspace) {
+        for (size_t g0 = 0; g0 < act.size(); g0 += SPMM_MAXV) {
+            const int nv = (int)std::min<size_t>(SPMM_MAXV, act.size() - g0);
+            operator_pass(act, g0, nv, B, nullptr, [&](int j) { return (const T*)bj(j); },
+                          [&](int j) { return Qj(j); }, [&](int) { return (T*)nullptr; });
+        }
+    } else {
+        for (int j = 0; j < nrhs; ++j)
+            HGM_HIP(hipMemcpyAsync(Qj(j), bj(j), sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+    }
+    for (int j = 0; j < nrhs; ++j) {
+        sumsq<T>(c, m, bj(j), scal + 3 * j);
+        if (xt_in) sumsq<T>(c, n, xtj(j), scal + 3 * j + 1);
+        sumsq<T>(c, dim, Qj(j), scal + 3 * j + 2);
+    }
+    std::vector<double> sh((size_t)3 * nrhs, 0.0);
+    {
+        Reader rd(c);
+        rd.add(sh.data(), scal, sizeof(T) * 3 * nrhs);
+        rd.go();
+    }
+    std::vector<double> nb(nrhs), nxt(nrhs), beta(nrhs);
+    for (int j = 0; j < nrhs; ++j) {
+        nb[j] = std::sqrt(sh[3 * (size_t)j]);
+        nxt[j] = xt_in ? std::sqrt(sh[3 * (size_t)j + 1]) : 0.0;
+        beta[j] = std::sqrt(sh[3 * (size_t)j + 2]);
+        div_scalar<T>(c, dim, Qj(j), Qj(j), (T)beta[j]);      // :13  Q(:,1) = r0 / beta
+    }
+
+    std::vector<double> H(hs * nrhs, 0.0);
+    auto Hh = [&](int j, int i, int k) -> double& { return H[hs * (size_t)j + (size_t)k * (maxit + 1) + i]; };
+    std::vector<char> x_assigned(nrhs, 0);
+    std::vector<double> Yh((size_t)maxit * nrhs, 0.0), mh((size_t)2 * nrhs, 0.0), y, rhs, M;
+    std::vector<int> next, ran;
+    bool unassigned = false;
+    for (int k = 0; k < maxit && !act.empty(); ++k) {
+        // ---- operator (*_bounds.m:25) over the running columns, repacked in groups of at most 8 ----
+        for (size_t g0 = 0; g0 < act.size(); g0 += SPMM_MAXV) {
+            const int nv = (int)std::min<size_t>(SPMM_MAXV, act.size() - g0);
+            auto qk = [&](int j) { return (const T*)(Qj(j) + (int64_t)k * ldq); };
+            if (nspace)    // A*q kept, B*(A*q) is the new basis vector
+                operator_pass(act, g0, nv, A, B, qk, [&](int j) { return Wj(j) + (int64_t)k * ldm; },
+                              [&](int j) { return Qj(j) + (int64_t)(k + 1) * ldq; });
+            else           // B*q and A*(B*q) kept; the latter is orthogonalised into the new basis vector
+                operator_pass(act, g0, nv, B, A, qk,
+                              [&](int j) { return const_cast<T*>(Vj(j)) + (int64_t)k * ldn; },
+                              [&](int j) { return Wj(j) + (int64_t)k * ldm; });
+        }
+        // ---- orthogonalisation (:26-32), the single solver's sweep once per running column ----
+        for (int j : act) {
+            ColTag tag(c, j);
+            T* Q = Qj(j);
+            T* v = Q + (int64_t)(k + 1) * ldq;
+            const T* src = nullptr;
+            if (!nspace) {
+                const T* w = Wj(j) + (int64_t)k * ldm;
+                if (orth == HGM_CGS2) HGM_HIP(hipMemcpyAsync(v, w, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+                else src = w;
+            }
+            T* Hcol = Hd + hs * (size_t)j + (size_t)k * (maxit + 1);
+            if (orth == HGM_CGS2) cgs2<T>(c, dim, Q, ldq, k, Hcol, false);
+            else mgs<T>(c, dim, Q, ldq, k, Hcol, false, src);
+        }
+        {
+            Reader rd(c);
+            for (int j : act) rd.add(&Hh(j, 0, k), Hd + hs * (size_t)j + (size_t)k * (maxit + 1), sizeof(T) * (k + 2));
+            rd.go();
+        }
+        // ---- projected solves (:34-36) on the host, per column ----
+        const int kk = k + 1;
+        next.clear();
+        ran.clear();
+        for (int j : act) {
+            if (Hh(j, k + 1, k) == 0) {                          // :31  breakdown of this column
+                // the single solver's convention: niters = k + 1, history entry k stays 0, x is the
+                // previous iterate (never assigned at k = 1)
+                if (err_hist) err_hist[(size_t)j * maxit + k] = 0.0;
+                if (res_hist) res_hist[(size_t)j * maxit + k] = 0.0;
+                niters[j] = k + 1;
+                if (k == 0) {
+                    unassigned = true;
+                    if (col_status) col_status[j] = HGM_E_NOT_ASSIGNED;
+                }
+                continue;
+            }
+            y.assign(kk, 0.0);
+            if (!hybrid) {
+                // yk = H(1:k+1,1:k) \ [beta; zeros(k,1)]   (*_nonhybrid_bounds.m:34-36)
+                M.assign((size_t)(kk + 1) * kk, 0.0);
+                for (int jj = 0; jj < kk; ++jj)
+                    for (int i = 0; i <= kk; ++i) M[(size_t)jj * (kk + 1) + i] = Hh(j, i, jj);
+                rhs.assign(kk + 1, 0.0);
+                rhs[0] = beta[j];
+                dense::qr_ls(kk + 1, kk, M.data(), rhs.data(), y.data());
+            } else {
+                // yk = (Hk'*Hk + lambda*eye(k)) \ (Hk'*tk)   (*_hybrid_bounds.m:34-36)
+                M.assign((size_t)kk * kk, 0.0);
+                for (int i = 0; i < kk; ++i)
+                    for (int jj = 0; jj < kk; ++jj) {
+                        double s = 0;
+                        for (int r = 0; r <= kk; ++r) s += Hh(j, r, i) * Hh(j, r, jj);
+                        M[(size_t)jj * kk + i] = s + (i == jj ? lambdas[j] : 0.0);
+                    }
+                rhs.assign(kk, 0.0);
+                for (int i = 0; i < kk; ++i) rhs[i] = Hh(j, 0, i) * beta[j];
+                dense::mldivide_square(kk, M.data(), rhs.data(), y.data());
+            }
+            std::memcpy(&Yh[(size_t)j * maxit], y.data(), sizeof(double) * kk);
+            ran.push_back(j);
+        }
+        // ---- monitors (:37-41) from the kept products: x = V_k y, ||x - x_true||^2, ||b - W_k y||^2 ----
+        if (!ran.empty()) {
+            h2d(c, Yd, Yh.data(), sizeof(T) * Yh.size());
+            for (int j : ran) {
+                recon<T>(c, n, kk, Vj(j), ldv, Yd + (size_t)j * maxit, xj(j), xtj(j), mon + 2 * j + 1, m, Wj(j), ldm,
+                         bj(j), mon + 2 * j);
+                x_assigned[j] = 1;
+            }
+            Reader rm(c);
+            rm.add(mh.data(), mon, sizeof(T) * 2 * nrhs);
+            rm.go();
+        }
+        for (int j : ran) {
+            const double res = std::sqrt(mh[2 * (size_t)j]) / nb[j];
+            if (res_hist) res_hist[(size_t)j * maxit + k] = res;
+            if (err_hist && xt_in) err_hist[(size_t)j * maxit + k] = std::sqrt(mh[2 * (size_t)j + 1]) / nxt[j];
+            if (res <= tol || kk == maxit) niters[j] = kk;        // :79-83  this column leaves the batch
+            else next.push_back(j);
+        }
+        act.swap(next);
+    }
+    if (X_out)
+        for (int j = 0; j < nrhs; ++j)
+            if (x_assigned[j]) stage_out_n<T>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
+    if (o && o->H_out) std::memcpy(o->H_out, H.data(), sizeof(double) * H.size());
+    if (unassigned)
+        throw Error{HGM_E_NOT_ASSIGNED, "Output argument \"x\" not assigned in at least one column (breakdown at k = 1)"};
     return HGM_OK;
 }
 

@@ -85,6 +85,7 @@ _SIGS = {
     "hgm_mat_destroy": (None, [c_void_p]),
     "hgm_spmv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgm_spmv_ab": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hgm_spmm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64]),
     "hgm_proj_norms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp, dp]),
     "hgm_proj_norms_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp]),
     "hgm_fused_plan_info": (c_int, [c_void_p, c_void_p, c_void_p, dp, P(C.c_uint64), ip64, P(c_int)]),
@@ -104,6 +105,8 @@ _SIGS = {
     "hgm_gmres_bounds_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, c_double, c_int, c_int, dp, dp, dp, P(c_int)]),
     "hgm_gmres_bounds_sweep": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, c_int, c_int,
                                        dp, dp, dp, dp, P(c_int), P(c_int)]),
+    "hgm_gmres_bounds_batch": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, c_int64, c_int, dp, c_int64, c_double,
+                                       c_int, dp, c_int, c_int, dp, c_int64, dp, dp, P(c_int), P(c_int)]),
     "hgm_lsqr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, P(c_int)]),
     "hgm_lsmr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, dp, P(c_int)]),
     "hgm_arnoldi": (c_int, [c_void_p, c_void_p, c_void_p, dp, c_int, c_int, c_double, c_int, dp, dp, P(c_int)]),

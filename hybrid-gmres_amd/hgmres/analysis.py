@@ -127,3 +127,64 @@ def error_surface(A, B, b, x_true, lambdas, maxit, tol=1e-10, *, ctx=None) -> di
         k, l = np.unravel_index(int(np.nanargmin(surf)), surf.shape)     # :45-46
         out[f"optimal_{side}"] = {"k": int(k) + 1, "lambda": float(lam[l]), "error": float(surf[k, l])}
     return out
+
+
+def error_vs_noise_level(A, B, b_exact, x_true, noise_levels, *, maxit, tol=1e-6, k_gcv=20, lambdas=None, seed=0,
+                         ctx=None) -> dict:
+    """The numeric part of ``plot_error_vs_noise_level.m:28-54``: the final errors of the four ``*_bounds``
+    solvers over a range of data noise levels, every solver's loop over the levels as ONE batched solve
+    (:func:`hgmres.core.gmres_bounds_batch`: the right-hand sides share the operator passes) instead of one
+    device solve per level and solver.
+
+    Right-hand side i is ``b_exact + noise_i / ||noise_i|| * noise_levels[i] * ||b_exact||`` (``:31-32``) with
+    ``noise_i`` drawn in order from ``numpy.random.default_rng(seed).standard_normal`` (not MATLAB's
+    ``rng(0); randn`` stream, which cannot be reproduced here).  The hybrid solvers' lambdas are the GCV
+    minimisers of ``:38-39`` / ``:43-44`` (``arnoldi`` + ``gcv_fminbnd`` per level and side, on [1e-9, 1e-1]
+    with TolX 1e-8) unless ``lambdas = (lambdas_ab, lambdas_ba)`` supplies them.  The GCV Arnoldis still run
+    one right-hand side at a time (batching them is follow-up work).
+
+    Returns ``noise_levels``, the noisy ``Bm`` (``m x nlevels``), ``lambda_gcv_ab`` / ``lambda_gcv_ba`` and the
+    curves ``final_errors_hab``, ``final_errors_hba``, ``final_errors_nab``, ``final_errors_nba``
+    (``err(end)`` of each solve, ``:41,46,49,52``) with the matching ``niters_*``."""
+    levels = np.asarray(noise_levels, dtype=np.float64).reshape(-1)
+    nl = levels.size
+    if nl < 1:
+        raise ValueError("noise_levels is empty")
+    m, n = A.shape
+    b_exact = np.asarray(b_exact, dtype=np.float64).reshape(-1)
+    x_true = np.asarray(x_true, dtype=np.float64).reshape(-1)
+    if b_exact.size != m or x_true.size != n:
+        raise ValueError(f"b_exact / x_true have lengths {b_exact.size} / {x_true.size}, expected {m} / {n}")
+    if lambdas is not None:
+        lab, lba = (np.asarray(v, dtype=np.float64).reshape(-1) for v in lambdas)
+        if lab.size != nl or lba.size != nl:
+            raise ValueError(f"lambdas: one value per noise level ({nl}) and side")
+    rng = np.random.default_rng(seed)
+    nbe = np.linalg.norm(b_exact)
+    Bm = np.empty((m, nl), order="F")
+    for i, level in enumerate(levels):                         # :29-32
+        noise = rng.standard_normal(m)
+        Bm[:, i] = b_exact + noise / np.linalg.norm(noise) * level * nbe
+    ctx = ctx or (A.ctx if isinstance(A, core.SparseOperator) else core.default_context())
+    Ao = core.as_operator(A, ctx)                              # uploaded once, reused by every solve
+    Bo = core.as_operator(B, ctx)
+    if lambdas is None:                                        # :34-39 / :43-44
+        lab, lba = np.zeros(nl), np.zeros(nl)
+        for side, lam in (("ab", lab), ("ba", lba)):
+            trace_m = m if side == "ab" else n                 # gcv_function.m:46-50
+            for i in range(nl):
+                H, beta, _ = core.arnoldi(Ao, Bo, Bm[:, i], k_gcv, side, ctx=ctx)
+                lam[i] = core.gcv_fminbnd(H, beta, trace_m, 1e-9, 1e-1, 1e-8)[0]
+    out = {"noise_levels": levels, "Bm": Bm, "lambda_gcv_ab": lab, "lambda_gcv_ba": lba}
+    for key, side, lam in (("hab", "ab", lab), ("hba", "ba", lba), ("nab", "ab", None), ("nba", "ba", None)):
+        fin, nit = np.full(nl, np.nan), np.zeros(nl, dtype=int)
+        for lo in range(0, nl, 64):                            # at most 64 columns per call
+            hi = min(nl, lo + 64)
+            R = core.gmres_bounds_batch(Ao, Bo, Bm[:, lo:hi], x_true, tol, maxit, side,
+                                        lambdas=None if lam is None else lam[lo:hi], ctx=ctx)
+            ok = R.niters >= 1
+            fin[lo:hi][ok] = R.error_norm[R.niters[ok] - 1, np.nonzero(ok)[0]]     # err(end), :41 / :46 / :49 / :52
+            nit[lo:hi] = R.niters
+        out[f"final_errors_{key}"] = fin
+        out[f"niters_{key}"] = nit
+    return out

@@ -438,6 +438,39 @@ def spmv_ab(A: "SparseOperator", B: "SparseOperator", q):
     return bq.astype(np.float64), abq.astype(np.float64)
 
 
+def spmm(A: "SparseOperator", X):
+    """``A @ X`` for an ``n x nvec`` host array ``X`` (``1 <= nvec <= 8``) through ``hgm_spmm``: the
+    operator's entries are read once for all columns (spmm.hip).  fp64 operators.  A column's bits do not
+    depend on ``nvec``, on its position, or on the other columns."""
+    m, n = A.shape
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    if X.ndim != 2 or X.shape[0] != n:
+        raise ValueError(f"X has shape {X.shape}, expected ({n}, nvec)")
+    nv = X.shape[1]
+    if not 1 <= nv <= 8:
+        raise ValueError(f"spmm takes 1 to 8 vectors, not {nv}")
+    if A.dtype != L.HGM_F64:
+        raise ValueError("spmm: fp64 operators only")
+    ctx = A.ctx
+    lib = L.load()
+    Xf = np.asfortranarray(X)
+    Y = np.empty((m, nv), order="F")
+    ptr = [C.c_void_p() for _ in range(2)]
+    try:
+        for p_, k in zip(ptr, (n * nv, m * nv)):
+            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, k), C.byref(p_)), ctx)
+        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
+        _check(lib.hgm_spmm(ctx.handle, A._h, nv, ptr[0], max(n, 1), ptr[1], max(m, 1)), ctx)
+        _check(lib.hgm_memcpy_d2h(ctx.handle, Y.ctypes.data_as(C.c_void_p), ptr[1], 8 * m * nv), ctx)
+    finally:
+        for p_ in ptr:
+            if p_.value:
+                lib.hgm_dev_free(ctx.handle, p_)
+    return Y
+
+
 def fused_plan_info(A: "SparseOperator", B: "SparseOperator"):
     """The one-pass plan of (A, B) under the context's options (built if needed): dict with the
     build seconds, a checksum over every plan array, the partial slots and whether the device built
@@ -659,6 +692,71 @@ def gmres_lambda_sweep(A, B, b, x_true, tol, maxit, lambdas, side, *, ctx=None, 
     return SweepResult(lam, err.reshape(shp).T.copy(), res.reshape(shp).T.copy(), sol.reshape(shp).T.copy(),
                        nit.astype(int), X.reshape(nl, n).T.copy() if return_x else None,
                        H.reshape(maxit, maxit + 1).T.copy() if return_H else None, ks.value)
+
+
+class BatchResult:
+    """Outputs of :func:`gmres_bounds_batch`.  ``x``: ``n x nrhs`` (a column that broke down at k = 1 is
+    NaN); ``error_norm``, ``residual_norm``: ``maxit x nrhs`` (row k-1 = iteration k; NaN past
+    ``niters[j]``); ``niters``, ``status`` (``HGM_OK`` or ``HGM_E_NOT_ASSIGNED``): per column; ``H``:
+    ``nrhs x (maxit+1) x maxit`` when requested, else None."""
+
+    def __init__(self, x, error_norm, residual_norm, niters, status, H):
+        self.x, self.error_norm, self.residual_norm = x, error_norm, residual_norm
+        self.niters, self.status, self.H = niters, status, H
+
+
+def gmres_bounds_batch(A, B, Bm, x_true, tol, maxit, side, *, lambdas=None, ctx=None, orth="mgs", return_H=False):
+    """``nrhs`` lockstep solves of one ``*_bounds`` solver against one operator pair
+    (``hgm_gmres_bounds_batch``): column j of every output is what ``{AB,BA}gmres_{hybrid,nonhybrid}_bounds``
+    returns for ``b = Bm[:, j]``, ``x_true[:, j]`` and ``lambdas[j]``.  ``side`` is 'ab' or 'ba';
+    ``lambdas=None`` selects the non-hybrid solver.  ``x_true`` is ``n x nrhs``, one vector shared by every
+    column, or None (the error histories stay NaN).  The operators' entries are read once per group of up
+    to 8 running columns and iteration; a finished column leaves the batch.  A column that breaks down at
+    k = 1 does not raise: its ``status`` is ``HGM_E_NOT_ASSIGNED`` and the other columns finish."""
+    sd = _side(side)
+    m, n = A.shape
+    maxit = int(maxit)
+    Bm = np.asarray(Bm, dtype=np.float64)
+    if Bm.ndim == 1:
+        Bm = Bm.reshape(-1, 1)
+    if Bm.ndim != 2 or Bm.shape[0] != m or Bm.shape[1] < 1:
+        raise ValueError(f"Bm has shape {Bm.shape}, expected ({m}, nrhs)")
+    nrhs = Bm.shape[1]
+    if nrhs > 64:
+        raise ValueError(f"at most 64 right-hand sides per call, not {nrhs}")
+    lam = None
+    if lambdas is not None:
+        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+        if lam.size != nrhs:
+            raise ValueError(f"lambdas has {lam.size} entries, expected one per right-hand side ({nrhs})")
+    xt, ldxt = None, 0
+    if x_true is not None:
+        xt = np.asarray(x_true, dtype=np.float64)
+        if xt.ndim == 1 or (xt.ndim == 2 and xt.shape[1] == 1 and nrhs != 1):
+            xt = _f64(xt, n, "x_true")                              # one column shared by every right-hand side
+        elif xt.shape != (n, nrhs):
+            raise ValueError(f"x_true has shape {xt.shape}, expected ({n},) or ({n}, {nrhs})")
+        else:
+            xt, ldxt = np.asfortranarray(xt), max(n, 1)
+    if maxit < 1:
+        raise ValueError("maxit must be >= 1")
+    ctx, Ao, Bo = _ops(A, B, ctx)
+    Bf = np.asfortranarray(Bm)
+    X = np.full((n, nrhs), np.nan, order="F")
+    err = np.full((maxit, nrhs), np.nan, order="F")
+    res = np.full((maxit, nrhs), np.nan, order="F")
+    nit = np.zeros(nrhs, dtype=np.int32)
+    st = np.zeros(nrhs, dtype=np.int32)
+    H = np.zeros((maxit + 1) * maxit * nrhs) if return_H else None
+    o = _opts(orth, H)
+    ip = C.POINTER(C.c_int)
+    rc = L.load().hgm_gmres_bounds_batch(ctx.handle, C.byref(o), Ao._h, Bo._h, _dp(Bf), max(m, 1), nrhs, _dp(xt), ldxt,
+                                         float(tol), maxit, _dp(lam), sd, 0 if lam is None else 1, _dp(X), max(n, 1),
+                                         _dp(err), _dp(res), nit.ctypes.data_as(ip), st.ctypes.data_as(ip))
+    if rc != L.HGM_E_NOT_ASSIGNED:
+        _check(rc, ctx)
+    return BatchResult(X, err, res, nit.astype(int), st.astype(int),
+                       H.reshape(nrhs, maxit, maxit + 1).transpose(0, 2, 1).copy() if return_H else None)
 
 
 def proj_norms(V, Y, t=None, *, ctx=None, loop=False):

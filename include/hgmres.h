@@ -21,6 +21,8 @@
  *                               pattern of plot_gcv_surface.m:58-122)
  *   hgm_gmres_bounds_sweep   <- the lambda loops of analyze_regularization.m:22-33 / plot_error_surface.m:28-42
  *                               over *_hybrid_bounds.m (one Arnoldi for every lambda)
+ *   hgm_gmres_bounds_batch   <- the loop over the noise levels of plot_error_vs_noise_level.m:28-54 over the
+ *                               four *_bounds.m (many right-hand sides, one operator pair)
  *   hgm_gmres_bounds_filter  <- outputs 5-8 of the four *_bounds.m (phi/dphi filter-factor bounds,
  *                               eig(M) of :4-9 replaced by device Ritz pairs)
  *   hgm_mat_create_csc       <- MATLAB sparse (CSC, jc/ir/pr) operand hand-over
@@ -307,6 +309,12 @@ HGM_API int hgm_spmv(hgm_ctx* ctx, const hgm_mat* A, const void* x_dev, void* y_
  * in the reference pixel order, as hgm_spmv's. */
 HGM_API int hgm_spmv_ab(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, const void* q_dev, void* Bq_dev,
                         void* ABq_dev);
+/* Y(:,r) = A*X(:,r), r < nvec, 1 <= nvec <= 8; X is cols x nvec and Y rows x nvec, column-major device
+ * pointers with leading dimensions ldx >= cols, ldy >= rows, reference pixel order as hgm_spmv.  The
+ * operator's entries are read ONCE for all nvec vectors.  fp64 operators only.  Fixed summation order:
+ * a column's bits do not depend on nvec, on its position, or on the other columns. */
+HGM_API int hgm_spmm(hgm_ctx*, const hgm_mat* A, int nvec, const double* X_dev, int64_t ldx,
+                     double* Y_dev, int64_t ldy);
 /* Multi-coefficient projected norms (the monitors of hgm_gmres_bounds_sweep), on device pointers:
  * V is rows x k column-major with leading dimension ldv >= rows, Y is k x nlam column-major (ldy >= k),
  * t has rows entries (NULL: zeros).  For every column l, in ONE pass over V (the rows x nlam product is
@@ -397,6 +405,25 @@ HGM_API int hgm_gmres_bounds_sweep(hgm_ctx* ctx, const hgm_opts* opts, const hgm
                                    const double* lambdas, int nlam, int side, double* X,
                                    double* error_surf, double* residual_surf, double* solnorm_surf,
                                    int* niters, int* ksteps);
+/* nrhs lockstep solves of one *_bounds solver (side, hybrid) against one operator pair: column j of every
+ * output is what hgm_gmres_bounds_ex(b = Bm(:,j), x_true = XT(:,j), lambda = lambdas[j]) returns.
+ * (The loop over the noise levels of plot_error_vs_noise_level.m:28-54; per iteration the operators'
+ * entries are read once per group of up to 8 running columns, hgm_spmm's kernel.)
+ * Bm: m x nrhs (host, ldb >= m).  x_true: n x nrhs (ldxt >= n), one shared column (ldxt == 0), or NULL
+ * (the error histories stay NaN).  lambdas: nrhs entries, required with hybrid = 1, ignored (may be NULL)
+ * otherwise.  error_hist / residual_hist: maxit x nrhs column-major, NaN past niters[j].  X: n x nrhs
+ * (ldx >= n), reference pixel order.  opts: orth is honoured; H_out receives nrhs consecutive
+ * (maxit+1) x maxit Hessenbergs.  Every column has its own stopping iteration and follows the single
+ * solver's breakdown convention; a finished column leaves the batch.  A column that breaks down at
+ * k = 1 gets col_status[j] = HGM_E_NOT_ASSIGNED (col_status is optional), niters[j] = 1 and its X column
+ * is left untouched; the others finish normally and the call returns HGM_E_NOT_ASSIGNED, else HGM_OK.
+ * Refused: HGM_E_ARG for fp32 operators, parity mode, HGM_DEVICE_PTRS, nrhs < 1 or > 64, and with
+ * hybrid = 1 a negative or non-finite lambda; HGM_E_UNSUPPORTED on a communicator or a context with a
+ * host all-reduce hook. */
+HGM_API int hgm_gmres_bounds_batch(hgm_ctx*, const hgm_opts*, const hgm_mat* A, const hgm_mat* B,
+        const double* Bm, int64_t ldb, int nrhs, const double* x_true, int64_t ldxt, double tol, int maxit,
+        const double* lambdas, int side, int hybrid, double* X, int64_t ldx,
+        double* error_hist, double* residual_hist, int* niters, int* col_status);
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* ctx, const hgm_opts* opts, const hgm_mat* A,
                                const hgm_mat* At, const double* b, const double* x_true, double tol,
                                int maxit, double* x, double* error_norm, double* residual_norm,
@@ -457,7 +484,8 @@ HGM_API int hgm_eig(int n, const double* A, double* wr, double* wi, double* V);
 /* Average device time (ms) of the named kernel class over the calls since the
  * last reset, measured with HIP events on the context stream.  classes:
  * 0 = SpMV on A (ray-major), 1 = SpMV on B/Aᵀ (pixel-major), 2 = MGS pass, 3 = the one-pass A*(B*q),
- * 4 = the launches of a hgm_proj_norms / hgm_proj_norms_loop call.
+ * 4 = the launches of a hgm_proj_norms / hgm_proj_norms_loop call, 5 = the launches of an hgm_spmm
+ * product, pack/unpack included (and each operator pass group of hgm_gmres_bounds_batch).
  * enable: 0 = off, 1 = every class, HGM_TIMING_CLASSES(mask) = only the classes whose
  * bit is set (each timed launch carries events, so time only what is read). */
 #define HGM_TIMING_CLASSES(mask) (0x100 | (mask))

@@ -23,6 +23,12 @@
  *        plot_error_surface.m:28-42 over {AB,BA}gmres_hybrid_bounds from ONE Arnoldi (hgm_gmres_bounds_sweep):
  *        maxit x nlam surfaces (NaN past niters(l)), X n x nlam; x_true may be [] (error_surf NaN).  The sweep
  *        runs the production kernels whatever the 'parity' setting (it has no fixed-order form).
+ *   hgmres_mex('gmres_bounds_batch', side,hybrid, A,B,Bm,x_true,tol,maxit[,lambdas])
+ *        -> [X, error_hist, residual_hist, niters, status]   the loop over the right-hand sides of
+ *        plot_error_vs_noise_level.m:28-54 over one {AB,BA}gmres_{hybrid,nonhybrid}_bounds solver as ONE lockstep
+ *        batch (hgm_gmres_bounds_batch): column j is the solve of Bm(:,j) with lambdas(j); x_true is n x 1 (shared),
+ *        n x nrhs or []; maxit x nrhs histories (NaN past niters(j)); status(j) ~= 0 marks a column whose x was never
+ *        assigned (its X column is NaN).  Always the production kernels (the batch has no parity form).
  *   hgmres_mex('device', d)                      select the HIP device (default 0)
  *   hgmres_mex('parity', 'auto'|'on'|'off')      summation orders (below; default 'auto')
  *
@@ -457,6 +463,70 @@ static void lambda_sweep(int nlhs, mxArray* plhs[], const mxArray* prhs[]) {
     if (nlhs > 4) plhs[4] = X;
 }
 
+/* [X, error_hist, residual_hist, niters, status] = hgmres_mex('gmres_bounds_batch', side, hybrid, A, B, Bm, x_true,
+ * tol, maxit [, lambdas]).  Side, hybrid, every size and the lambdas are checked before a device is touched. */
+static void bounds_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    const int side = side_of(prhs[1]);
+    const int hybrid = scalar(prhs[2], "hybrid") != 0.0;
+    need_double(prhs[3], "A");
+    need_double(prhs[4], "B");
+    const int64_t m = (int64_t)mxGetM(prhs[3]), n = (int64_t)mxGetN(prhs[3]);
+    if ((int64_t)mxGetM(prhs[4]) != n || (int64_t)mxGetN(prhs[4]) != m)
+        fail("hgmres:arg", "hgmres: B must be size(A')");
+    need_double(prhs[5], "Bm");
+    const int64_t nb = (int64_t)mxGetN(prhs[5]);
+    if (mxIsSparse(prhs[5]) || (int64_t)mxGetM(prhs[5]) != m || nb < 1 || nb > 64)
+        fail("hgmres:arg", "hgmres: Bm must be a dense size(A,1) x nrhs matrix with 1 <= nrhs <= 64");
+    const double* xt = NULL;
+    int64_t ldxt = 0;
+    if (!mxIsEmpty(prhs[6])) {
+        need_double(prhs[6], "x_true");
+        const int64_t xm = (int64_t)mxGetM(prhs[6]), xn = (int64_t)mxGetN(prhs[6]);
+        if (mxIsSparse(prhs[6]) || xm != n || (xn != 1 && xn != nb))
+            fail("hgmres:arg", "hgmres: x_true must be dense, size(A,2) x 1 or size(A,2) x nrhs, or []");
+        xt = mxGetDoubles(prhs[6]);
+        ldxt = xn == 1 && nb != 1 ? 0 : n;
+    }
+    const double tol = scalar(prhs[7], "tol");
+    const int maxit = maxit_of(prhs[8]);
+    const double* lam = NULL;
+    if (hybrid) {
+        if (nrhs < 10) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per right-hand side)");
+        need_double(prhs[9], "lambdas");
+        if (mxIsSparse(prhs[9]) || (int64_t)mxGetNumberOfElements(prhs[9]) != nb)
+            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per right-hand side");
+        lam = mxGetDoubles(prhs[9]);
+        for (int64_t j = 0; j < nb; ++j)
+            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
+    }
+    hgm_mat* A = op(prhs[3], "A");
+    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
+    hgm_mat* B = op(prhs[4], "B");
+    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nb, mxREAL);
+    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
+    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
+    int* nit = (int*)mxCalloc((size_t)nb, sizeof(int));
+    int* cst = (int*)mxCalloc((size_t)nb, sizeof(int));
+    for (int64_t i = 0; i < n * nb; ++i) mxGetDoubles(X)[i] = (double)NAN;
+    const int st = hgm_gmres_bounds_batch(ctx(), NULL, A, B, mxGetDoubles(prhs[5]), m > 0 ? m : 1, (int)nb, xt, ldxt, tol,
+                                          maxit, lam, side, hybrid, mxGetDoubles(X), n > 0 ? n : 1, mxGetDoubles(e),
+                                          mxGetDoubles(r), nit, cst);
+    if (st != HGM_E_NOT_ASSIGNED) check(st);             /* unassigned columns are reported in status */
+    mxArray* ni = mxCreateDoubleMatrix((mwSize)nb, 1, mxREAL);
+    mxArray* cs = mxCreateDoubleMatrix((mwSize)nb, 1, mxREAL);
+    for (int64_t j = 0; j < nb; ++j) {
+        mxGetDoubles(ni)[j] = (double)nit[j];
+        mxGetDoubles(cs)[j] = (double)cst[j];
+    }
+    mxFree(nit);
+    mxFree(cst);
+    plhs[0] = X;
+    if (nlhs > 1) plhs[1] = e;
+    if (nlhs > 2) plhs[2] = r;
+    if (nlhs > 3) plhs[3] = ni;
+    if (nlhs > 4) plhs[4] = cs;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char fn[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], fn, sizeof fn) != 0)
@@ -488,6 +558,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(fn, "gmres_bounds")) {
         nargs(nrhs, 9, 12, fn);
         bounds(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(fn, "gmres_bounds_batch")) {
+        nargs(nrhs, 8, 9, fn);
+        bounds_batch(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(fn, "gmres_lambda_sweep")) {
         nargs(nrhs, 8, 8, fn);
         lambda_sweep(nlhs, plhs, prhs);
