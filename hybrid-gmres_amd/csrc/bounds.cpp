@@ -24,22 +24,7 @@
 
 namespace hgm {
 
-// solvers.cpp
-struct GmresSpec {
-    int side;
-    int proj;
-    bool lambda_in_op;
-    bool x_preassigned;
-};
-int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B,
-                 const double* b_in, const double* xt_in, double tol, int maxit, double lambda, double* x_out,
-                 double* err_out, double* res_out, int* niters);
-
 namespace {
-
-enum { PROJ_LS = 0, PROJ_PTR = 1 };
-
-inline int64_t round64(int64_t x) { return (x + 63) / 64 * 64; }
 
 // ritz_steps = 0 runs the full Arnoldi (p = dim, the eigenpairs of M) up to this dimension
 constexpr int64_t kRitzFullDim = 1024;
@@ -62,7 +47,7 @@ struct DeltaM {
 // G = Qb(:,0:cnt-1)' * DeltaM * Qb(:,0:cnt-1) (cnt x cnt, column-major, host)
 std::vector<double> projected_delta(hgm_ctx* c, const DeltaM& dm, const double* Qb, int64_t ldq, int64_t dim,
                                     int cnt) {
-    const int64_t ldw = round64(dim);
+    const int64_t ldw = round_up(dim, 64);
     double* W = c->buf<double>("fb_W", (size_t)ldw * cnt);
     double* Gd = c->buf<double>("fb_G", (size_t)cnt * cnt);
     for (int j = 0; j < cnt; ++j) dm.apply(c, Qb + (int64_t)j * ldq, W + (int64_t)j * ldw);
@@ -108,8 +93,9 @@ int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const h
     std::vector<double> H((size_t)(maxit + 1) * maxit, 0.0);
     o2.H_out = H.data();
     int k = 0;
+    KrylovBasis kb{};
     int st = gmres_family(c, GmresSpec{side, hybrid ? PROJ_PTR : PROJ_LS, false, false}, &o2, A, B, b, xt, tol, maxit,
-                          hybrid ? lambda : 0.0, x_out, err_out, res_out, &k);
+                          hybrid ? lambda : 0.0, x_out, err_out, res_out, &k, &kb);
     if (st != HGM_OK) return st;
     if (o && o->H_out) std::memcpy(o->H_out, H.data(), sizeof(double) * H.size());
     if (niters) *niters = k;
@@ -119,12 +105,9 @@ int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const h
     const bool broke = Hh(k, k - 1) == 0.0;
     const int kf = broke ? k - 1 : k;
 
-    // the solve's basis Q(:,0:k), read with gmres_family's own leading dimension: an n-space basis
-    // on a communicator (a one-rank RCCL context included) is laid out for the sharded path
-    const int64_t ldq = krylov_ld(c, dim, nspace && (c->world > 1 || c->nccl != nullptr));
-    const double* Q = c->buf<double>("Q", (size_t)ldq * (maxit + 1));
-    // ---- dK = Qk' * DeltaM * Qk for every k at once (the leading blocks of the final one) ----
-    const std::vector<double> dK = kf > 0 ? projected_delta(c, dm, Q, ldq, dim, kf) : std::vector<double>();
+    // ---- dK = Qk' * DeltaM * Qk for every k at once (the leading blocks of the final one), on the
+    // solve's own basis Q(:,0:k) ----
+    const std::vector<double> dK = kf > 0 ? projected_delta(c, dm, kb.Q, kb.ld, kb.dim, kf) : std::vector<double>();
 
     // ---- leading eigenpairs of M: p-step Arnoldi with CGS2 (replaces eig(M), :4-9) ----
     // default: p = dim (eig(M) itself, to rounding) wherever that is cheap -- the reference's own
@@ -133,9 +116,9 @@ int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const h
     p = (int)std::min<int64_t>(std::max(p, kf), dim);
     std::vector<double> mu(std::max(kf, 1)), dmu(std::max(kf, 1)), rres(std::max(kf, 1));
     if (kf > 0) {
-        const int64_t ldp = krylov_ld(c, dim, false);
-        double* Qp = c->buf<double>("fb_Qp", (size_t)ldp * (p + 1));
-        if (krylov_padded(c, ldp)) HGM_HIP(hipMemsetAsync(Qp, 0, sizeof(double) * ldp * (p + 1), c->stream));
+        const KrylovBasis kp = krylov_basis(c, "fb_Qp", dim, p + 1, false);
+        double* Qp = kp.Q;
+        const int64_t ldp = kp.ld;
         double* Hd = c->buf<double>("fb_H", (size_t)(p + 1) * p + 8);
         double* hsink = c->buf<double>("fb_hsink", (size_t)p + 8);
         double* tm = c->buf<double>("fb_t", std::max(A->rows, A->cols) + 1);
@@ -154,17 +137,8 @@ int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const h
         int j0 = 0;
         while (j0 < p) {
             for (int j = j0; j < p; ++j) {
-                const double* qj = Qp + (int64_t)j * ldp;
-                double* v = Qp + (int64_t)(j + 1) * ldp;
-                if (nspace) {                                    // M = B*A
-                    spmv<double>(c, A, qj, tm, EPI_NONE, 0.0, nullptr, KC_SPMV_A);
-                    spmv<double>(c, B, tm, v, EPI_NONE, 0.0, nullptr, KC_SPMV_B);
-                } else if (fplan) {                              // M = A*B, one pass over B
-                    fused_ab(c, B, fplan, qj, tm, v);
-                } else {                                         // M = A*B
-                    spmv<double>(c, B, qj, tm, EPI_NONE, 0.0, nullptr, KC_SPMV_B);
-                    spmv<double>(c, A, tm, v, EPI_NONE, 0.0, nullptr, KC_SPMV_A);
-                }
+                // M*q_j, single rank (a one-rank communicator included): no collective
+                apply_M(c, A, B, fplan, nspace, Qp + (int64_t)j * ldp, tm, Qp + (int64_t)(j + 1) * ldp, false);
                 cgs2<double>(c, dim, Qp, ldp, j, Hd + (size_t)j * (p + 1), false);
             }
             Reader rd(c);

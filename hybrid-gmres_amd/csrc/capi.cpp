@@ -19,43 +19,6 @@
 
 namespace hgm {
 
-// solvers.cpp
-struct GmresSpec {
-    int side;
-    int proj;
-    bool lambda_in_op;
-    bool x_preassigned;
-};
-int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B,
-                 const double* b_in, const double* xt_in, double tol, int maxit, double lambda, double* x_out,
-                 double* err_out, double* res_out, int* niters);
-template <typename T>
-int lsqr_t(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*, const double*, double, int,
-           bool, double, double*, double*, double*, int*);
-template <typename T>
-int lsmr_t(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*, const double*, double, int,
-           double*, double*, double*, double*, int*);
-int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b_in,
-                const double* xt_in, double tol, int maxit, double lambda, double* x_out, double* err_out,
-                double* res_out, int* niters);
-int arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const double* b_in, int kg, int side, double btol,
-            int orth, double* H_out, double* beta_out, int* kdone);
-int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b_in,
-                       const double* xt_in, double tol, int maxit, const double* lambdas, int nlam, int side,
-                       double* X_out, double* err_surf, double* res_surf, double* sol_surf, int* niters,
-                       int* ksteps);
-int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
-                       int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
-                       const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
-                       double* res_hist, int* niters, int* col_status);
-// bounds.cpp
-int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
-                        const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
-                        const hgm_mat* dML, const hgm_mat* dMR, int ritz_steps, double* x_out, double* err_out,
-                        double* res_out, int* niters, double* phi, double* dphi, double* mu_out, double* ritz_res);
-
-enum { PROJ_LS = 0, PROJ_PTR = 1, PROJ_ABRTP = 2 };
-
 void DevBuf::ensure(size_t b) {
     if (b <= bytes) return;
     release();

@@ -180,18 +180,44 @@ void svd_values(int n, const double* Min, double* s) {
     std::sort(s, s + n, [](double a, double b) { return a > b; });
 }
 
-// gcv_function.m:33-58 on a cached H ((k+1) x k, leading dimension ldh)
-double gcv_from_H(const double* H, int ldh, int k, double beta, double lambda, double trace_m) {
-    const double eps = std::numeric_limits<double>::epsilon();
-    std::vector<double> HtH((size_t)k * k), rhs(k), y(k);
+void normal_matrix(const double* H, int ldh, int k, double* G) {
     for (int i = 0; i < k; ++i)
         for (int j = 0; j < k; ++j) {
             double s = 0;
             for (int r = 0; r <= k; ++r) s += AT(H, ldh, r, i) * AT(H, ldh, r, j);
-            AT(HtH.data(), k, i, j) = s + (i == j ? lambda : 0.0);   // :38  Hk'*Hk + lambda*eye(k)
+            AT(G, k, i, j) = s;
         }
+}
+
+void proj_ptr(const double* G, const double* H, int ldh, int k, double beta, double lambda, double* y) {
+    std::vector<double> M(G, G + (size_t)k * k), rhs(k);
+    for (int i = 0; i < k; ++i) AT(M.data(), k, i, i) += lambda;
     for (int i = 0; i < k; ++i) rhs[i] = AT(H, ldh, 0, i) * beta;    // Hk'*tk, tk = beta e1
-    mldivide_square(k, HtH.data(), rhs.data(), y.data());
+    mldivide_square(k, M.data(), rhs.data(), y);
+}
+
+void proj_ls(const double* H, int ldh, int k, double beta, double* y) {
+    std::vector<double> M((size_t)(k + 1) * k), rhs(k + 1, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int i = 0; i <= k; ++i) AT(M.data(), k + 1, i, j) = AT(H, ldh, i, j);
+    rhs[0] = beta;
+    qr_ls(k + 1, k, M.data(), rhs.data(), y);
+}
+
+void proj_gram(const double* G, int ldg, const double* c, int k, double lambda, double* y) {
+    std::vector<double> M((size_t)k * k);
+    for (int j = 0; j < k; ++j)
+        for (int i = 0; i <= j; ++i) AT(M.data(), k, i, j) = AT(M.data(), k, j, i) = AT(G, ldg, i, j);
+    for (int i = 0; i < k; ++i) AT(M.data(), k, i, i) += lambda;
+    mldivide_square(k, M.data(), c, y);
+}
+
+// gcv_function.m:33-58 on a cached H ((k+1) x k, leading dimension ldh)
+double gcv_from_H(const double* H, int ldh, int k, double beta, double lambda, double trace_m) {
+    const double eps = std::numeric_limits<double>::epsilon();
+    std::vector<double> G((size_t)k * k), y(k);
+    normal_matrix(H, ldh, k, G.data());
+    proj_ptr(G.data(), H, ldh, k, beta, lambda, y.data());           // :38
     double rn = 0;                                                   // :40 norm(tk - Hk*yk)^2
     for (int r = 0; r <= k; ++r) {
         double t = (r == 0 ? beta : 0.0);

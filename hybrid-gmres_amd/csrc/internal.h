@@ -635,6 +635,71 @@ void sync(hgm_ctx* c);
 void timing_begin(hgm_ctx* c, int cls, hipEvent_t* start);
 void timing_end(hgm_ctx* c, int cls, hipEvent_t start, double bytes);
 
+// ---------------- solvers (solvers.cpp, bounds.cpp) ----------------
+enum Proj { PROJ_LS = 0, PROJ_PTR = 1, PROJ_ABRTP = 2 };
+struct GmresSpec {
+    int side;             // HGM_SIDE_BA: n-space Krylov of B*A (+λI) ; HGM_SIDE_AB: m-space of A*B
+    int proj;             // Proj
+    bool lambda_in_op;    // RTP: operator B*(A*v) + lambda*v
+    bool x_preassigned;   // hybrid_ba_gmres_rtp.m:4 initialises x = zeros
+};
+inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+// sharded code path: world > 1, or a one-rank RCCL communicator (hgm_ctx_create_dist)
+inline bool dist_n(const hgm_ctx* c) { return c->world > 1 || c->nccl != nullptr; }
+// A Krylov basis in a named workspace buffer: cols vectors of length dim, ld = krylov_ld(dim, dist)
+// apart, zeroed when that pads them (krylov_padded).
+struct KrylovBasis {
+    double* Q;
+    int64_t ld, dim;
+    int cols;
+};
+KrylovBasis krylov_basis(hgm_ctx* c, const char* name, int64_t dim, int cols, bool dist);
+// Q(:,0) = r0 = B*b (n-space, B*A) or b (m-space, A*B); ss (optional, device) = ||r0||^2, summed over
+// the pixel shards on a communicator
+void start_residual(hgm_ctx* c, const hgm_mat* B, const double* b, bool nspace, const KrylovBasis& kb, double* ss);
+// out = M*q with no epilogue: n-space B*(A*q), keep = A*q; m-space A*(B*q), keep = B*q (fplan: both
+// in one pass over B).  comm: all-reduce A's product over a communicator's ranks, as apply_A does
+// (false: a single-rank caller, which issues no collective on a one-rank communicator either)
+void apply_M(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const FusedPlan* fplan, bool nspace, const double* q,
+             double* keep, double* out, bool comm = true);
+// basis_out (optional): the solve's basis Q(:,0:k), valid until the context's next solve
+int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B,
+                 const double* b_in, const double* xt_in, double tol, int maxit, double lambda, double* x_out,
+                 double* err_out, double* res_out, int* niters, KrylovBasis* basis_out = nullptr);
+template <typename T>
+int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b_in,
+           const double* xt_in, double tol, int maxit, bool hybrid, double lambda, double* x_out,
+           double* err_out, double* res_out, int* niters);
+template <typename T>
+int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b_in,
+           const double* xt_in, double tol, int maxit, double* x_out, double* err_out, double* res_out,
+           double* ar_out, int* iters);
+extern template int lsqr_t<double>(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*,
+                                   const double*, double, int, bool, double, double*, double*, double*, int*);
+extern template int lsqr_t<float>(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*,
+                                  const double*, double, int, bool, double, double*, double*, double*, int*);
+extern template int lsmr_t<double>(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*,
+                                   const double*, double, int, double*, double*, double*, double*, int*);
+extern template int lsmr_t<float>(hgm_ctx*, const hgm_opts*, const hgm_mat*, const hgm_mat*, const double*,
+                                  const double*, double, int, double*, double*, double*, double*, int*);
+int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b_in,
+                const double* xt_in, double tol, int maxit, double lambda, double* x_out, double* err_out,
+                double* res_out, int* niters);
+int arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const double* b_in, int kg, int side, double btol,
+            int orth, double* H_out, double* beta_out, int* kdone);
+int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b_in,
+                       const double* xt_in, double tol, int maxit, const double* lambdas, int nlam, int side,
+                       double* X_out, double* err_surf, double* res_surf, double* sol_surf, int* niters,
+                       int* ksteps);
+int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
+                       int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
+                       const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
+                       double* res_hist, int* niters, int* col_status);
+int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
+                        const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
+                        const hgm_mat* dML, const hgm_mat* dMR, int ritz_steps, double* x_out, double* err_out,
+                        double* res_out, int* niters, double* phi, double* dphi, double* mu_out, double* ritz_res);
+
 // ---------------- dense host LA (dense.cpp) ----------------
 namespace dense {
 // MATLAB mldivide for square M (col-major n x n): symmetric + positive diagonal ->
@@ -644,6 +709,16 @@ void mldivide_square(int n, const double* M, const double* b, double* x);
 void qr_ls(int m, int n, const double* M, const double* b, double* x);
 // singular values of a square n x n matrix (one-sided Jacobi), descending.
 void svd_values(int n, const double* M, double* s);
+// Projected solves on Hk = H(1:k+1,1:k) (leading dimension ldh), tk = beta e1; G and y are k x k / k.
+// G = Hk'*Hk
+void normal_matrix(const double* H, int ldh, int k, double* G);
+// yk = (G + lambda*eye(k)) \ (Hk'*tk)   (*_hybrid_bounds.m:34-36, gcv_function.m:38)
+void proj_ptr(const double* G, const double* H, int ldh, int k, double beta, double lambda, double* y);
+// yk = Hk \ tk   (hybrid_ba_gmres_rtp.m:28-29, *_nonhybrid_bounds.m:34-36)
+void proj_ls(const double* H, int ldh, int k, double beta, double* y);
+// yk = (AQk'*AQk + lambda*eye(k)) \ (AQk'*b)   (hybrid_ab_gmres_rtp.m:32): G's columns (ldg apart) hold
+// the upper triangle of AQk'*AQk, c = AQk'*b
+void proj_gram(const double* G, int ldg, const double* c, int k, double lambda, double* y);
 double gcv_from_H(const double* H, int ldh, int k, double beta, double lambda, double trace_m);
 // MATLAB fminbnd (Brent / Forsythe-Malcolm-Moler fmin) of gcv_from_H over [lo, hi].
 double gcv_fminbnd(const double* H, int k, double beta, double trace_m, double lo, double hi,

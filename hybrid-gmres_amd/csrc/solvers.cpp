@@ -26,7 +26,11 @@ namespace {
 
 constexpr double EPSD = std::numeric_limits<double>::epsilon();
 
-inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+// 0: the m-space Gram error monitor's side dot x_true'(B*q_k) stays with the MGS sweep instead of
+// riding the one pass over B (the A/B build of DESIGN.md §3.5)
+#ifndef HGM_FUSED_ZX
+#define HGM_FUSED_ZX 1
+#endif
 
 // Scalar slots in ctx->dscal.
 enum Slot { S_NB = 0, S_NXT = 1, S_BETA = 2, S_RES = 3, S_ERR = 4, S_ALPHA = 5, S_AR = 6, S_FRO = 7,
@@ -36,9 +40,6 @@ template <typename T>
 T* dslot(hgm_ctx* c, int i) {
     return reinterpret_cast<T*>(c->dscal) + i;
 }
-
-// sharded code path: world > 1, or a one-rank RCCL communicator (hgm_ctx_create_dist)
-inline bool dist_n(hgm_ctx* c) { return c->world > 1 || c->nccl != nullptr; }
 
 // y = A x (+epilogue) where the output is an m-vector assembled across ranks.
 template <typename T>
@@ -193,16 +194,45 @@ void check_dims(const hgm_mat* A, const hgm_mat* B) {
 }  // namespace
 
 // ============================================================================
+// Krylov start and plain operator step shared by the Arnoldi-based solvers
+// ============================================================================
+KrylovBasis krylov_basis(hgm_ctx* c, const char* name, int64_t dim, int cols, bool dist) {
+    KrylovBasis kb{nullptr, krylov_ld(c, dim, dist), dim, cols};
+    kb.Q = c->buf<double>(name, (size_t)kb.ld * cols);
+    if (krylov_padded(c, kb.ld)) HGM_HIP(hipMemsetAsync(kb.Q, 0, sizeof(double) * kb.ld * cols, c->stream));
+    return kb;
+}
+
+void start_residual(hgm_ctx* c, const hgm_mat* B, const double* b, bool nspace, const KrylovBasis& kb, double* ss) {
+    // hybrid_*_rtp.m:7,9 / gcv_function.m:8 / *_bounds.m:11-13: BA: r0 = B*(b - A*0) ; AB: r0 = b - A*(B*0) = b
+    if (nspace) apply_B<double>(c, B, b, kb.Q, EPI_NONE, 0.0, nullptr);
+    else HGM_HIP(hipMemcpyAsync(kb.Q, b, sizeof(double) * kb.dim, hipMemcpyDeviceToDevice, c->stream));
+    if (!ss) return;
+    if (nspace) nsumsq<double>(c, kb.dim, kb.Q, ss);
+    else sumsq<double>(c, kb.dim, kb.Q, ss);
+}
+
+void apply_M(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const FusedPlan* fplan, bool nspace, const double* q,
+             double* keep, double* out, bool comm) {
+    const bool ar = comm && dist_n(c);
+    if (nspace) {                                                              // B*(A*q)
+        spmv<double>(c, A, q, keep, EPI_NONE, 0.0, nullptr, KC_SPMV_A);
+        if (ar) allreduce(c, keep, A->rows);
+        spmv<double>(c, B, keep, out, EPI_NONE, 0.0, nullptr, KC_SPMV_B);
+        return;
+    }
+    if (fplan) {                                                               // A*(B*q), one pass over B
+        fused_ab(c, B, fplan, q, keep, out);
+    } else {
+        spmv<double>(c, B, q, keep, EPI_NONE, 0.0, nullptr, KC_SPMV_B);
+        spmv<double>(c, A, keep, out, EPI_NONE, 0.0, nullptr, KC_SPMV_A);
+    }
+    if (ar) allreduce(c, out, A->rows);
+}
+
+// ============================================================================
 // GMRES family (Arnoldi + projected solve)
 // ============================================================================
-enum Proj { PROJ_LS = 0, PROJ_PTR = 1, PROJ_ABRTP = 2 };
-
-struct GmresSpec {
-    int side;             // HGM_SIDE_BA: n-space Krylov of B*A (+λI) ; HGM_SIDE_AB: m-space of A*B
-    int proj;             // Proj
-    bool lambda_in_op;    // RTP: operator B*(A*v) + lambda*v
-    bool x_preassigned;   // hybrid_ba_gmres_rtp.m:4 initialises x = zeros
-};
 
 // Ring polling (single GPU): the host waits for step k by watching the entries of ring
 // slot k turn from a NaN sentinel into values instead of an event recorded after the step.
@@ -255,7 +285,7 @@ static void ring_wait(hgm_ctx* c, const double* ring, const std::vector<size_t>&
 
 int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B,
                  const double* b_in, const double* xt_in, double tol, int maxit, double lambda, double* x_out,
-                 double* err_out, double* res_out, int* niters) {
+                 double* err_out, double* res_out, int* niters, KrylovBasis* basis_out) {
     check_dims(A, B);
     solver_guard(c);
     HGM_REQUIRE(B != nullptr, "B is NULL");
@@ -267,7 +297,6 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     const long waits0 = c->waits;
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
     c->path_mon.clear();
-    using T = double;
     const bool dev = o && (o->flags & HGM_DEVICE_PTRS);
     const int orth = o ? o->orth : HGM_MGS;
     const int64_t m = A->rows, n = A->cols;
@@ -278,29 +307,30 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     // fixed summation orders; every fused or reformulated monitor below is switched off
     const bool parity = c->num.parity;
     HGM_REQUIRE(!parity || (!dist_n(c) && po.trivial()), "parity mode: single rank, reference pixel order");
-    const int64_t ldq = krylov_ld(c, dim, dist);
     hipStream_t st = c->stream;
 
-    T* Q = c->buf<T>("Q", (size_t)ldq * (maxit + 1));
-    if (krylov_padded(c, ldq)) HGM_HIP(hipMemsetAsync(Q, 0, sizeof(T) * ldq * (maxit + 1), st));
-    T* x = c->buf<T>("x", n > 0 ? n : 1);
-    T* t = c->buf<T>("t_m", m > 0 ? m : 1);        // m-vector scratch (A*q, residual)
-    T* tn = c->buf<T>("t_n", n > 0 ? n : 1);       // n-vector scratch (AB side: B*q)
-    T* z = c->buf<T>("z_m", m > 0 ? m : 1);        // AB side: z = Q*y
-    T* tr = c->buf<T>("t_res", m > 0 ? m : 1);     // m-vector of the residual monitor (aux stream)
+    const KrylovBasis kb = krylov_basis(c, "Q", dim, maxit + 1, dist);
+    if (basis_out) *basis_out = kb;
+    double* Q = kb.Q;
+    const int64_t ldq = kb.ld;
+    double* x = c->buf<double>("x", n > 0 ? n : 1);
+    double* t = c->buf<double>("t_m", m > 0 ? m : 1);        // m-vector scratch (A*q, residual)
+    double* tn = c->buf<double>("t_n", n > 0 ? n : 1);       // n-vector scratch (AB side: B*q)
+    double* z = c->buf<double>("z_m", m > 0 ? m : 1);        // AB side: z = Q*y
+    double* tr = c->buf<double>("t_res", m > 0 ? m : 1);     // m-vector of the residual monitor (aux stream)
     const int64_t ldaq = round_up(m > 0 ? m : 1, 64);
     // n-space side: keep the operator's products A*Q(:,j) (the RTP Gram matrix needs them,
     // and the residual monitor b - A*x = b - (A*Q) y reuses them instead of another SpMV)
     const bool reuse = !(o && (o->flags & HGM_EXPLICIT_RESIDUAL)) && !parity;
     const bool aq_res = nspace && reuse;
-    T* AQ = (sp.proj == PROJ_ABRTP || aq_res) ? c->buf<T>("AQ", (size_t)ldaq * maxit) : nullptr;
+    double* AQ = (sp.proj == PROJ_ABRTP || aq_res) ? c->buf<double>("AQ", (size_t)ldaq * maxit) : nullptr;
     // m-space side: keep B*Q(:,j) and A*(B*Q(:,j)) (the latter is the new Arnoldi vector
     // before orthogonalisation), so x = B*(Q y) = (B*Q) y and b - A*x = b - (A*B*Q) y are
     // GEMVs over k kept columns instead of two SpMVs per iteration (*_bounds.m:37-40)
     const bool bq_res = !nspace && reuse;
     const int64_t ldbq = round_up(n > 0 ? n : 1, 64);
-    T* BQ = bq_res ? c->buf<T>("BQ", (size_t)ldbq * maxit) : nullptr;
-    T* ABQ = bq_res ? c->buf<T>("ABQ", (size_t)ldaq * maxit) : nullptr;
+    double* BQ = bq_res ? c->buf<double>("BQ", (size_t)ldbq * maxit) : nullptr;
+    double* ABQ = bq_res ? c->buf<double>("ABQ", (size_t)ldaq * maxit) : nullptr;
     // Per-iteration exchange ring in pinned host memory: slot k holds
     // [H(:,k) | Gram column k, AQk'b] (LH doubles), the monitors [res^2, err^2] of
     // iteration k, and the projected solution y_k.  Single GPU: the kernels write the
@@ -372,15 +402,15 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
             for (size_t i = offS; i < offS + 3; ++i) r[i] = RING_SENTINEL;
         for (size_t i = offQG; i < ring_n; ++i) r[i] = RING_SENTINEL;
     }
-    T* dr = zc ? c->hring_dev : c->buf<T>("ring_dev", ring_n);
+    double* dr = zc ? c->hring_dev : c->buf<double>("ring_dev", ring_n);
     auto publish = [&](size_t off, size_t cnt) {
         if (!zc)
-            HGM_HIP(hipMemcpyAsync(c->hring + off, dr + off, sizeof(T) * cnt, hipMemcpyDeviceToHost, c->stream));
+            HGM_HIP(hipMemcpyAsync(c->hring + off, dr + off, sizeof(double) * cnt, hipMemcpyDeviceToHost, c->stream));
     };
     // inputs staged after the ring reset (its stream sync then finds the GPU idle)
-    const T* b = stage_in<T>(c, "in_b", b_in, m, dev);
-    const T* xt = stage_in_n<T>(c, "in_xt", xt_in, n, dev, po);
-    fill<T>(c, n, x, T(0));
+    const double* b = stage_in<double>(c, "in_b", b_in, m, dev);
+    const double* xt = stage_in_n<double>(c, "in_xt", xt_in, n, dev, po);
+    fill<double>(c, n, x, 0.0);
 
     std::vector<double> H((size_t)(maxit + 1) * maxit, 0.0);
     std::vector<double> err(maxit, 0.0), res(maxit, 0.0);
@@ -389,7 +419,7 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     // ||b|| (m, replicated) and ||x_true|| (n, sharded) — MATLAB recomputes them every
     // iteration (hybrid_*_rtp.m:32-33); the values are loop-invariant.
     double nb = 0, nxt = 0, beta = 0, xt2 = 0;
-    T* q0 = Q;
+    double* q0 = Q;
     // (a communicator all-reduces the x_true norm over the pixel shards: the second branch, whatever
     // stream the reconstructions use)
     if (poll && dev && rs_stream != st && !dist_n(c)) {
@@ -397,42 +427,35 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
         // iteration 0) and r0 is divided on the device.  With device inputs the two norms
         // run on the aux stream, beside B*b (x_true in the caller's order: same norm).
         StreamScope scope(c, rs_stream, "aux:");
-        sumsq<T>(c, m, b, dr + offS + 1);
-        sumsq<T>(c, n, reinterpret_cast<const T*>(xt_in), dr + offS + 2);   // ||x_true - 0||^2
+        sumsq<double>(c, m, b, dr + offS + 1);
+        sumsq<double>(c, n, xt_in, dr + offS + 2);   // ||x_true - 0||^2
     } else if (poll && dist_n(c)) {
-        sumsq<T>(c, m, b, dr + offS + 1);                    // (m: replicated)
-        sumsq<T>(c, n, xt, dslot<T>(c, S_NXT));              // ||x_true - 0||^2 over the pixel shards
-        allreduce(c, dslot<T>(c, S_NXT), 1);
-        copy_sys(c, dslot<T>(c, S_NXT), dr + offS + 2);
+        sumsq<double>(c, m, b, dr + offS + 1);                    // (m: replicated)
+        sumsq<double>(c, n, xt, dslot<double>(c, S_NXT));              // ||x_true - 0||^2 over the pixel shards
+        allreduce(c, dslot<double>(c, S_NXT), 1);
+        copy_sys(c, dslot<double>(c, S_NXT), dr + offS + 2);
     } else if (poll) {
-        sumsq<T>(c, m, b, dr + offS + 1);
-        sumsq<T>(c, n, xt, dr + offS + 2);                   // ||x_true - 0||^2
+        sumsq<double>(c, m, b, dr + offS + 1);
+        sumsq<double>(c, n, xt, dr + offS + 2);                   // ||x_true - 0||^2
     } else {
-        sumsq<T>(c, m, b, dslot<T>(c, S_NB));
-        nsumsq_diff<T>(c, n, xt, x, dslot<T>(c, S_NXT));   // ||x_true - 0||^2
+        sumsq<double>(c, m, b, dslot<double>(c, S_NB));
+        nsumsq_diff<double>(c, n, xt, x, dslot<double>(c, S_NXT));   // ||x_true - 0||^2
     }
-    // r0
-    if (nspace) {
-        apply_B<T>(c, B, b, q0, EPI_NONE, T(0), nullptr);   // d = B*b   (hybrid_*_rtp.m:7,9; *_bounds r0 = B*(b - A*0))
-    } else {
-        HGM_HIP(hipMemcpyAsync(q0, b, sizeof(T) * m, hipMemcpyDeviceToDevice, st));   // r0 = b - A*(B*0) = b
-    }
+    start_residual(c, B, b, nspace, kb, poll ? nullptr : dslot<double>(c, S_BETA));   // r0
     if (poll) {
-        normalize_to<T>(c, dim, q0, dr + offS);           // :10,:13  beta = norm(r0); Q(:,1) = r0 / beta
+        normalize_to<double>(c, dim, q0, dr + offS);           // :10,:13  beta = norm(r0); Q(:,1) = r0 / beta
     } else {
-        if (nspace) nsumsq<T>(c, dim, q0, dslot<T>(c, S_BETA));
-        else sumsq<T>(c, dim, q0, dslot<T>(c, S_BETA));
         read_scalars(c, 0, 3);
         nb = std::sqrt(c->hscal[S_NB]);
         nxt = std::sqrt(c->hscal[S_NXT]);
         xt2 = c->hscal[S_NXT];
         beta = std::sqrt(c->hscal[S_BETA]);               // :10  beta = norm(r0)
-        div_scalar<T>(c, dim, q0, q0, (T)beta);           // :13  Q(:,1) = r0 / beta
+        div_scalar<double>(c, dim, q0, q0, beta);           // :13  Q(:,1) = r0 / beta
     }
 
     bool x_assigned = sp.x_preassigned;
     int k = 0;
-    std::vector<double> y, rhs, M;
+    std::vector<double> y, M;
     std::vector<double> G((size_t)maxit * maxit, 0.0), cvec(maxit, 0.0);
     // Gram error monitor: Q'Q, Q'x_true and the errors it produced (-1: formed explicitly)
     // (m-space: the Gram of Z = B*Q, from H and the strictly lower Q'Q in SQ)
@@ -453,78 +476,77 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     // measured ~1.4 % slower at C4 than the scale pass it replaces)
     const bool pn_ok = !dist && orth == HGM_MGS && c->num.pend_norm >= 1 && !parity &&
                        (nspace ? spmv_pn_ok(A, EPI_DIVH) && spmv_pn_ok(B, EPI_ADDQ)
-                               : c->num.pend_norm == 2 && std::is_same_v<T, double> && fplan != nullptr &&
-                                     fused_pend_ok(c, fplan) && !krylov_padded(c, ldq));
-    PendNorm<T> pend;                                  // np > 0: Q(:,next step) awaits its division
-    T* pn_h = c->buf<T>("pn_h", 2);
+                               : c->num.pend_norm == 2 && fplan != nullptr && fused_pend_ok(c, fplan) &&
+                                     !krylov_padded(c, ldq));
+    PendNorm<double> pend;                                  // np > 0: Q(:,next step) awaits its division
+    double* pn_h = c->buf<double>("pn_h", 2);
     // Enqueue Arnoldi step kq: operator application + orthogonalisation (+ Gram column).
     auto enqueue_step = [&](int kq) {
         bool zx_fused = false;                            // x_true'(B*q_k) formed by the fused pass
         bool zx_rode = false;                             // ... and summed over the ranks with A*(B*q_k)
-        T* qk = Q + (int64_t)kq * ldq;
-        T* v = Q + (int64_t)(kq + 1) * ldq;
+        double* qk = Q + (int64_t)kq * ldq;
+        double* v = Q + (int64_t)(kq + 1) * ldq;
         const bool pending_in = pend.np > 0;
         // ---- operator (hybrid_*_rtp.m:19 ; *_bounds.m:25) ----
         if (nspace && pending_in) {
-            T* Aq = AQ ? AQ + (int64_t)kq * ldaq : t;
-            PendNorm<T> pa = pend;
+            double* Aq = AQ ? AQ + (int64_t)kq * ldaq : t;
+            PendNorm<double> pa = pend;
             pa.hdev = pn_h;
             pa.hring = dr + (size_t)(kq - 1) * LH + kq;    // H(kq, kq-1) of step kq-1
-            spmv<T>(c, A, qk, Aq, EPI_DIVH, T(0), nullptr, KC_SPMV_A, nullptr, &pa);   // A*q = (A*v)/h
-            PendNorm<T> pb;
+            spmv<double>(c, A, qk, Aq, EPI_DIVH, 0.0, nullptr, KC_SPMV_A, nullptr, &pa);   // A*q = (A*v)/h
+            PendNorm<double> pb;
             pb.hdev = pn_h;
             // B*(A*q) + lambda*q with q = v/h (lambda = 0: B*(A*q) + 0*q); the MGS dots kernel
             // writes q back over v
-            spmv<T>(c, B, Aq, v, EPI_ADDQ, T(sp.lambda_in_op ? lambda : 0.0), qk, KC_SPMV_B, nullptr, &pb);
+            spmv<double>(c, B, Aq, v, EPI_ADDQ, sp.lambda_in_op ? lambda : 0.0, qk, KC_SPMV_B, nullptr, &pb);
         } else if (nspace) {
-            T* Aq = AQ ? AQ + (int64_t)kq * ldaq : t;
-            apply_A<T>(c, A, qk, Aq, EPI_NONE, T(0), nullptr);
-            if (sp.lambda_in_op) apply_B<T>(c, B, Aq, v, EPI_ADD, T(lambda), qk);   // B*(A*v) + lambda*v
-            else apply_B<T>(c, B, Aq, v, EPI_NONE, T(0), nullptr);                  // B*(A*v)
+            double* Aq = AQ ? AQ + (int64_t)kq * ldaq : t;
+            if (sp.lambda_in_op) {
+                apply_A<double>(c, A, qk, Aq, EPI_NONE, 0.0, nullptr);
+                apply_B<double>(c, B, Aq, v, EPI_ADD, lambda, qk);                  // B*(A*v) + lambda*v
+            } else {
+                apply_M(c, A, B, nullptr, true, qk, Aq, v);                         // B*(A*v)
+            }
         } else {
-            T* Bq = BQ ? BQ + (int64_t)kq * ldbq : tn;
+            double* Bq = BQ ? BQ + (int64_t)kq * ldbq : tn;
             // A*(B*Q(:,k)) lands in its kept column (MGS reads it from there and writes the
             // orthogonalised vector to Q(:,k+1), no copy), or in Q(:,k+1) for CGS2
-            T* w = (ABQ && orth != HGM_CGS2) ? ABQ + (int64_t)kq * ldaq : v;
+            double* w = (ABQ && orth != HGM_CGS2) ? ABQ + (int64_t)kq * ldaq : v;
             if (fplan) {
                 // both in one pass over B; with the m-space Gram error monitor the pass also forms
                 // the side dot x_true'(B*Q(:,k)) (else the MGS sweep's extra workgroups do)
-#ifndef HGM_FUSED_ZX
-#define HGM_FUSED_ZX 1
-#endif
                 const bool zxf = HGM_FUSED_ZX && gem_ab;
                 // (on a communicator the rank-local dot goes to a device slot, all-reduced below)
-                T* zx_dst = zxf ? (dist_n(c) ? dslot<T>(c, S_AUX2) : dr + offQG + (size_t)kq * LQ + kq + 2) : nullptr;
+                double* zx_dst =
+                    zxf ? (dist_n(c) ? dslot<double>(c, S_AUX2) : dr + offQG + (size_t)kq * LQ + kq + 2) : nullptr;
                 // on a communicator the side dot rides the m-vector all-reduce as its element m
                 // (when the column's stride leaves room past m): one collective per step, not two
                 const int64_t wld = (ABQ && orth != HGM_CGS2) ? ldaq : ldq;
                 const bool ride = zxf && dist_n(c) && wld > m;
-                PendNorm<T> pq;                                // q_k = v_k / H(k,k-1) as the pass stages it
+                PendNorm<double> pq;                                // q_k = v_k / H(k,k-1) as the pass stages it
                 if (pending_in) {
                     pq = pend;
                     pq.hdev = pn_h;
                     pq.hring = dr + (size_t)(kq - 1) * LH + kq;  // H(kq, kq-1) of step kq-1
                 }
-                if constexpr (std::is_same_v<T, double>)
-                    zx_fused = fused_ab(c, B, fplan, qk, Bq, w, zxf ? xt : nullptr, ride ? w + m : zx_dst,
-                                        pending_in ? &pq : nullptr);
+                zx_fused = fused_ab(c, B, fplan, qk, Bq, w, zxf ? xt : nullptr, ride ? w + m : zx_dst,
+                                    pending_in ? &pq : nullptr);
                 zx_rode = ride && zx_fused;
                 if (dist_n(c)) allreduce(c, w, zx_rode ? m + 1 : m);             // (as apply_A)
                 // (the all-reduced side dot goes into the ring with the MGS sweep below)
             } else {
-                apply_B<T>(c, B, qk, Bq, EPI_NONE, T(0), nullptr);                  // B*Q(:,k)
-                apply_A<T>(c, A, Bq, w, EPI_NONE, T(0), nullptr);                   // A*(B*Q(:,k))
+                apply_M(c, A, B, nullptr, false, qk, Bq, w);                        // B*Q(:,k), A*(B*Q(:,k))
             }
             if (ABQ && orth == HGM_CGS2)
-                HGM_HIP(hipMemcpyAsync(ABQ + (int64_t)kq * ldaq, v, sizeof(T) * m, hipMemcpyDeviceToDevice,
+                HGM_HIP(hipMemcpyAsync(ABQ + (int64_t)kq * ldaq, v, sizeof(double) * m, hipMemcpyDeviceToDevice,
                                        c->stream));
         }
         // ---- orthogonalisation (hybrid_*_rtp.m:20-26) ----
-        T* Hcol = dr + (size_t)kq * LH;                  // -> host H(:,k)
+        double* Hcol = dr + (size_t)kq * LH;                  // -> host H(:,k)
         // column k of AQk'*AQk and AQk'*b (hybrid_ab_gmres_rtp.m:31-32); A*Q(:,j) was
         // computed inside M_reg_op(Q(:,j)) at :19 — the same deterministic SpMV.  With MGS
         // it runs as extra workgroups of the sweep's first two passes.
-        MdotJob<T> gram;
+        MdotJob<double> gram;
         if (sp.proj == PROJ_ABRTP) {
             gram.n = m;
             gram.ncols = kq + 1;
@@ -534,35 +556,34 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
             gram.e = b;                                   // + b'*AQ(:,k)
             gram.out = Hcol + (maxit + 2);
         }
-        const MdotJob<T>* side = sp.proj == PROJ_ABRTP ? &gram : nullptr;
+        const MdotJob<double>* side = sp.proj == PROJ_ABRTP ? &gram : nullptr;
         if (orth == HGM_CGS2) {
-            cgs2<T>(c, dim, Q, ldq, kq, Hcol, dist);
-            if (side) multidot<T>(c, m, gram.ncols, AQ, ldaq, gram.w, gram.out, b);
+            cgs2<double>(c, dim, Q, ldq, kq, Hcol, dist);
+            if (side) multidot<double>(c, m, gram.ncols, AQ, ldaq, gram.w, gram.out, b);
         } else {
-            PendNorm<T>* defer = (pn_ok && kq + 1 < maxit) ? &pend : nullptr;
+            PendNorm<double>* defer = (pn_ok && kq + 1 < maxit) ? &pend : nullptr;
             if (!defer) pend.np = 0;
-            MdotJob<T> zx;                                // gem_ab: x_true'(B*q_k) -> row entry k+2
-            T* zx_ring = dr + offQG + (size_t)kq * LQ + kq + 2;
+            MdotJob<double> zx;                                // gem_ab: x_true'(B*q_k) -> row entry k+2
+            double* zx_ring = dr + offQG + (size_t)kq * LQ + kq + 2;
             if (gem_ab) {
                 zx.n = n;
                 zx.w = BQ + (int64_t)kq * ldbq;
                 zx.e = xt;
-                zx.out = dist_n(c) ? dslot<T>(c, S_AUX2) : zx_ring;   // (the fused pass's zx_dst too)
+                zx.out = dist_n(c) ? dslot<double>(c, S_AUX2) : zx_ring;   // (the fused pass's zx_dst too)
             }
             // the Gram row's extra dot: x_true (n-space) or b (m-space, unused: the row is for L)
             const double* cps = nullptr;
             double* cpd = nullptr;
-            if constexpr (std::is_same_v<T, double>)
-                if (zx_rode) {
-                    cps = reinterpret_cast<const double*>(ABQ ? ABQ + (int64_t)kq * ldaq + m : v + m);
-                    cpd = dr + offQG + (size_t)kq * LQ + kq + 2;
-                }
-            mgs<T>(c, dim, Q, ldq, kq, Hcol, dist, (!nspace && ABQ) ? ABQ + (int64_t)kq * ldaq : nullptr,
-                   gem_ab ? (zx_fused ? nullptr : &zx) : side, defer, pending_in ? (const T*)pn_h : nullptr,
-                   gem ? (gem_n ? xt : b) : nullptr, gem ? dr + offQG + (size_t)kq * LQ : nullptr, cps, cpd);
+            if (zx_rode) {
+                cps = ABQ ? ABQ + (int64_t)kq * ldaq + m : v + m;
+                cpd = dr + offQG + (size_t)kq * LQ + kq + 2;
+            }
+            mgs<double>(c, dim, Q, ldq, kq, Hcol, dist, (!nspace && ABQ) ? ABQ + (int64_t)kq * ldaq : nullptr,
+                        gem_ab ? (zx_fused ? nullptr : &zx) : side, defer, pending_in ? pn_h : nullptr,
+                        gem ? (gem_n ? xt : b) : nullptr, gem ? dr + offQG + (size_t)kq * LQ : nullptr, cps, cpd);
             if (gem_ab && dist_n(c) && !zx_rode) {        // x_true'(B*q_k) over the pixel shards
                 allreduce(c, zx.out, 1);
-                if constexpr (std::is_same_v<T, double>) copy_sys(c, zx.out, zx_ring);
+                copy_sys(c, zx.out, zx_ring);
             }
         }
         // Step kq-1's column is complete (H(kq,kq-1) came from this step's A product).  The
@@ -587,23 +608,22 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     auto enqueue_recon = [&](int kq, bool want_x) {
         StreamScope scope(c, (rs_aux_dist && want_x) ? st : rs_stream, (rs_aux_dist && want_x) ? "" : "aux:");
         const int kk = kq + 1;
-        const T* yk = c->hring_dev + offY + (size_t)kq * maxit;
-        T* rslot = dr + offM + 2 * (size_t)kq;
-        T* eslot = rslot + 1;
+        const double* yk = c->hring_dev + offY + (size_t)kq * maxit;
+        double* rslot = dr + offM + 2 * (size_t)kq;
+        double* eslot = rslot + 1;
         // an error sum over the pixel shards is all-reduced in a device slot, then copied into the
         // (host-mapped) ring
-        T* eloc = (dist_n(c) && zc) ? dslot<T>(c, S_ERR) : eslot;
+        double* eloc = (dist_n(c) && zc) ? dslot<double>(c, S_ERR) : eslot;
         auto err_done = [&](bool reduce) {
             if (reduce && dist_n(c)) allreduce(c, eloc, 1);
-            if constexpr (std::is_same_v<T, double>)
-                if (eloc != eslot) copy_sys(c, eloc, eslot);
+            if (eloc != eslot) copy_sys(c, eloc, eslot);
         };
         // ---- reconstruction (hybrid_*_rtp.m:30/33 ; *_bounds.m:37-38) ----
         if (aq_res) {
             // x = Q(:,1:k)*yk with ||x - x_true||^2 (:33/:36) and ||b - A*x||^2 (:32/:35)
             // evaluated as ||b - (A*Q(:,1:k))*yk||^2, all in one launch (+ finalize)
             // (want_x false: the Gram error monitor has the error, x is formed at the end)
-            recon<T>(c, n, kk, Q, ldq, yk, want_x ? x : nullptr, xt, eslot, m, AQ, ldaq, b, rslot);
+            recon<double>(c, n, kk, Q, ldq, yk, want_x ? x : nullptr, xt, eslot, m, AQ, ldaq, b, rslot);
             x_pending = want_x ? -1 : kq;
             if (dist_n(c)) allreduce(c, eslot, 1);
             publish(offM + 2 * (size_t)kq, 2);
@@ -614,7 +634,7 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
             // xk = B*(Q(:,1:k)*yk) = (B*Q(:,1:k))*yk with ||xk - x_true||^2, and
             // ||b - A*xk||^2 = ||b - (A*B*Q(:,1:k))*yk||^2 (*_bounds.m:37-40), one launch
             // (want_x false: the m-space Gram error monitor has the error, x is formed at the end)
-            recon<T>(c, n, kk, BQ, ldbq, yk, want_x ? x : nullptr, xt, eloc, m, ABQ, ldaq, b, rslot);
+            recon<double>(c, n, kk, BQ, ldbq, yk, want_x ? x : nullptr, xt, eloc, m, ABQ, ldaq, b, rslot);
             x_pending = want_x ? -1 : kq;
             if (want_x) err_done(true);
             publish(offM + 2 * (size_t)kq, 2);
@@ -623,20 +643,20 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
         }
         if (nspace) {
             // x = Q(:,1:k)*yk, fused with the error monitor ||x - x_true||^2 (:33 / :36)
-            gemv_err<T>(c, n, kk, Q, ldq, yk, x, xt, eslot);
+            gemv_err<double>(c, n, kk, Q, ldq, yk, x, xt, eslot);
             if (dist_n(c)) allreduce(c, eslot, 1);
         } else {
-            gemv<T>(c, m, kk, Q, ldq, yk, z, 0);                 // zk = Q(:,1:k)*yk
-            apply_B<T>(c, B, z, x, EPI_NONE, T(0), nullptr);     // xk = B*zk
-            sumsq_diff<T>(c, n, x, xt, eloc);
+            gemv<double>(c, m, kk, Q, ldq, yk, z, 0);                 // zk = Q(:,1:k)*yk
+            apply_B<double>(c, B, z, x, EPI_NONE, 0.0, nullptr);     // xk = B*zk
+            sumsq_diff<double>(c, n, x, xt, eloc);
             err_done(true);
         }
         // ---- monitors (hybrid_*_rtp.m:32-33 / :35-36): norm(b - A*x) ----
         if (!dist_n(c)) {
-            spmv<T>(c, A, x, tr, EPI_RSUB, T(0), b, KC_SPMV_A, rslot);   // sum of squares fused
+            spmv<double>(c, A, x, tr, EPI_RSUB, 0.0, b, KC_SPMV_A, rslot);   // sum of squares fused
         } else {
-            apply_A<T>(c, A, x, tr, EPI_RSUB, T(0), b);
-            sumsq<T>(c, m, tr, rslot);
+            apply_A<double>(c, A, x, tr, EPI_RSUB, 0.0, b);
+            sumsq<double>(c, m, tr, rslot);
         }
         publish(offM + 2 * (size_t)kq, 2);
         if (pipe_ev) pipe_record(c);
@@ -735,36 +755,13 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
         const int kk = k + 1;                            // MATLAB k
         y.assign(kk, 0.0);
         if (sp.proj == PROJ_LS) {
-            // yk = H(1:k+1,1:k) \ [beta; zeros(k,1)]   (hybrid_ba_gmres_rtp.m:28-29)
-            M.assign((size_t)(kk + 1) * kk, 0.0);
-            for (int j = 0; j < kk; ++j)
-                for (int i = 0; i <= kk; ++i) M[(size_t)j * (kk + 1) + i] = Hh(i, j);
-            rhs.assign(kk + 1, 0.0);
-            rhs[0] = beta;
-            dense::qr_ls(kk + 1, kk, M.data(), rhs.data(), y.data());
+            dense::proj_ls(H.data(), maxit + 1, kk, beta, y.data());
         } else if (sp.proj == PROJ_PTR) {
-            // yk = (Hk'*Hk + lambda*eye(k)) \ (Hk'*tk)   (*_hybrid_bounds.m:34-36)
             M.assign((size_t)kk * kk, 0.0);
-            for (int i = 0; i < kk; ++i)
-                for (int j = 0; j < kk; ++j) {
-                    double s = 0;
-                    for (int r = 0; r <= kk; ++r) s += Hh(r, i) * Hh(r, j);
-                    M[(size_t)j * kk + i] = s + (i == j ? lambda : 0.0);
-                }
-            rhs.assign(kk, 0.0);
-            for (int i = 0; i < kk; ++i) rhs[i] = Hh(0, i) * beta;
-            dense::mldivide_square(kk, M.data(), rhs.data(), y.data());
+            dense::normal_matrix(H.data(), maxit + 1, kk, M.data());
+            dense::proj_ptr(M.data(), H.data(), maxit + 1, kk, beta, lambda, y.data());
         } else {
-            // yk = (AQk'*AQk + lambda*eye(k)) \ (AQk'*b)   (hybrid_ab_gmres_rtp.m:32)
-            M.assign((size_t)kk * kk, 0.0);
-            for (int j = 0; j < kk; ++j)
-                for (int i = 0; i <= j; ++i) {
-                    const double g = G[(size_t)j * maxit + i];
-                    M[(size_t)j * kk + i] = g;
-                    M[(size_t)i * kk + j] = g;
-                }
-            for (int i = 0; i < kk; ++i) M[(size_t)i * kk + i] += lambda;
-            dense::mldivide_square(kk, M.data(), cvec.data(), y.data());
+            dense::proj_gram(G.data(), maxit, cvec.data(), kk, lambda, y.data());
         }
         std::memcpy(c->hring + offY + (size_t)k * maxit, y.data(), sizeof(double) * kk);
         bool want_x = true;
@@ -793,9 +790,9 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
         // the last reconstruction left x unformed (Gram error monitor): x = Q(:,0:k) y_k
         // behind it, on the same stream
         StreamScope scope(c, rs_stream, "aux:");
-        const T* yk = c->hring_dev + offY + (size_t)x_pending * maxit;
-        if (nspace) gemv<T>(c, n, x_pending + 1, Q, ldq, yk, x, 0);
-        else gemv<T>(c, n, x_pending + 1, BQ, ldbq, yk, x, 0);          // x = (B*Q) y
+        const double* yk = c->hring_dev + offY + (size_t)x_pending * maxit;
+        if (nspace) gemv<double>(c, n, x_pending + 1, Q, ldq, yk, x, 0);
+        else gemv<double>(c, n, x_pending + 1, BQ, ldbq, yk, x, 0);          // x = (B*Q) y
         x_pending = -1;
     }
     bool staged = false;
@@ -807,7 +804,7 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
         // (a communicator's last reconstruction formed x on the step stream: staged out there below)
         if (rs_stream != st && !rs_aux_dist && x_assigned && x_out != nullptr) {
             StreamScope scope(c, rs_stream, "aux:");
-            stage_out_n<T>(c, x_out, x, n, dev, po);     // ends with a sync of the aux stream
+            stage_out_n<double>(c, x_out, x, n, dev, po);     // ends with a sync of the aux stream
             staged = true;
         } else if (pipe_ev) {
             pipe_wait(c);
@@ -822,7 +819,7 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     const int nit = k + 1;                               // niters = k
     if (rs_stream != st) stream_sync(rs_stream);
     if (!x_assigned) throw Error{HGM_E_NOT_ASSIGNED, "Output argument \"x\" not assigned during call (breakdown at k = 1)"};
-    if (!staged) stage_out_n<T>(c, x_out, x, n, dev, po);
+    if (!staged) stage_out_n<double>(c, x_out, x, n, dev, po);
     if (c->host_stats) {
         const double tot = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         std::fprintf(stderr, "hgm gmres: %d iters, %.1f us total, %.1f us blocked in %ld waits\n", nit, tot * 1e6,
@@ -1501,62 +1498,56 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
     HGM_REQUIRE(!c->num.parity || (!dist_n(c) && po.trivial()), "parity mode: single rank, reference pixel order");
     HGM_REQUIRE(b_in != nullptr && xt_in != nullptr, "b and x_true are required");
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
-    using T = double;
     const bool dev = o && (o->flags & HGM_DEVICE_PTRS);
     const int64_t m = A->rows, n = A->cols;
     const int64_t ldv = round_up(n > 0 ? n : 1, 64);
-    const T* b = stage_in<T>(c, "in_b", b_in, m, dev);
-    const T* xt = stage_in_n<T>(c, "in_xt", xt_in, n, dev, po);
-    T* V = c->buf<T>("Q", (size_t)ldv * maxit);
-    T* x = c->buf<T>("x", n + 1);
-    T* u = c->buf<T>("u", m + 1);
-    T* t = c->buf<T>("t_m", m + 1);
-    T* yd = c->buf<T>("y", maxit + 8);
-    T* sl = reinterpret_cast<T*>(c->dscal);
-    fill<T>(c, n, x, T(0));
+    const double* b = stage_in<double>(c, "in_b", b_in, m, dev);
+    const double* xt = stage_in_n<double>(c, "in_xt", xt_in, n, dev, po);
+    double* V = c->buf<double>("Q", (size_t)ldv * maxit);
+    double* x = c->buf<double>("x", n + 1);
+    double* u = c->buf<double>("u", m + 1);
+    double* t = c->buf<double>("t_m", m + 1);
+    double* yd = c->buf<double>("y", maxit + 8);
+    double* sl = c->dscal;
+    fill<double>(c, n, x, 0.0);
     std::vector<double> err(maxit, 0.0), res(maxit, 0.0);
     std::vector<double> Bk((size_t)(maxit + 1) * maxit, 0.0);                  // :11
     auto BK = [&](int i, int j) -> double& { return Bk[(size_t)j * (maxit + 1) + i]; };
 
-    sumsq<T>(c, m, b, sl + S_NB);
-    nsumsq_diff<T>(c, n, xt, x, sl + S_NXT);
+    sumsq<double>(c, m, b, sl + S_NB);
+    nsumsq_diff<double>(c, n, xt, x, sl + S_NXT);
     read_scalars(c, 0, 2);
     const double nb = std::sqrt(c->hscal[S_NB]);
     const double nxt = std::sqrt(c->hscal[S_NXT]);
     const double beta1 = nb;                                                   // :7
-    div_scalar<T>(c, m, b, u, beta1);                                          // :8
-    T* v0 = V;
-    apply_B<T>(c, At, u, v0, EPI_NONE, 0.0, nullptr);                          // :13
-    nsumsq<T>(c, n, v0, sl + S_ALPHA);
-    double alpha1 = std::sqrt(read1<T>(c, sl + S_ALPHA));                      // :14
-    div_scalar<T>(c, n, v0, v0, alpha1);                                       // :15-16
+    div_scalar<double>(c, m, b, u, beta1);                                          // :8
+    double* v0 = V;
+    apply_B<double>(c, At, u, v0, EPI_NONE, 0.0, nullptr);                          // :13
+    nsumsq<double>(c, n, v0, sl + S_ALPHA);
+    double alpha1 = std::sqrt(read1<double>(c, sl + S_ALPHA));                      // :14
+    div_scalar<double>(c, n, v0, v0, alpha1);                                       // :15-16
     int k = 0;
     std::vector<double> Gm, G2, LHS, RHS, y;
     for (k = 0; k < maxit; ++k) {
-        T* vk = V + (int64_t)k * ldv;
+        double* vk = V + (int64_t)k * ldv;
         BK(k, k) = alpha1;                                                     // :23
-        apply_A<T>(c, A, vk, t, EPI_SUB, alpha1, u);                           // :24
-        sumsq<T>(c, m, t, sl + S_BETA);
-        const double beta_k = std::sqrt(read1<T>(c, sl + S_BETA));            // :25
-        div_scalar<T>(c, m, t, u, beta_k);                                     // :26
+        apply_A<double>(c, A, vk, t, EPI_SUB, alpha1, u);                           // :24
+        sumsq<double>(c, m, t, sl + S_BETA);
+        const double beta_k = std::sqrt(read1<double>(c, sl + S_BETA));            // :25
+        div_scalar<double>(c, m, t, u, beta_k);                                     // :26
         BK(k + 1, k) = beta_k;                                                 // :27
         if (k < maxit - 1) {                                                   // :29
-            T* vn = V + (int64_t)(k + 1) * ldv;
-            apply_B<T>(c, At, u, vn, EPI_SUB, beta_k, vk);                     // :30
-            nsumsq<T>(c, n, vn, sl + S_ALPHA);
-            const double a1 = std::sqrt(read1<T>(c, sl + S_ALPHA));            // :31
-            div_scalar<T>(c, n, vn, vn, a1);                                   // :32-33
+            double* vn = V + (int64_t)(k + 1) * ldv;
+            apply_B<double>(c, At, u, vn, EPI_SUB, beta_k, vk);                     // :30
+            nsumsq<double>(c, n, vn, sl + S_ALPHA);
+            const double a1 = std::sqrt(read1<double>(c, sl + S_ALPHA));            // :31
+            div_scalar<double>(c, n, vn, vn, a1);                                   // :32-33
             alpha1 = a1;                                                       // :34
         }
         const int kk = k + 1;
         // :37-44  LHS = (Bk'*Bk)^2 + (alpha_k1*beta_k1)^2 e1 e1' + lambda I ; RHS = B_k(1,1) beta1 (Bk'*Bk) e1
         Gm.assign((size_t)kk * kk, 0.0);
-        for (int i = 0; i < kk; ++i)
-            for (int j = 0; j < kk; ++j) {
-                double s = 0;
-                for (int r = 0; r <= kk; ++r) s += BK(r, i) * BK(r, j);
-                Gm[(size_t)j * kk + i] = s;
-            }
+        dense::normal_matrix(Bk.data(), maxit + 1, kk, Gm.data());                 // Bk'*Bk
         G2.assign((size_t)kk * kk, 0.0);
         for (int i = 0; i < kk; ++i)
             for (int j = 0; j < kk; ++j) {
@@ -1574,10 +1565,10 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
         y.assign(kk, 0.0);
         dense::mldivide_square(kk, LHS.data(), RHS.data(), y.data());          // :44
         h2d_pinned(c, yd, y.data(), sizeof(double) * kk);
-        gemv<T>(c, n, kk, V, ldv, yd, x, 0);                                   // :45
-        nsumsq_diff<T>(c, n, x, xt, sl + S_ERR);                               // :47
-        apply_A<T>(c, A, x, t, EPI_RSUB, 0.0, b);                              // :48
-        sumsq<T>(c, m, t, sl + S_RES);
+        gemv<double>(c, n, kk, V, ldv, yd, x, 0);                                   // :45
+        nsumsq_diff<double>(c, n, x, xt, sl + S_ERR);                               // :47
+        apply_A<double>(c, A, x, t, EPI_RSUB, 0.0, b);                              // :48
+        sumsq<double>(c, m, t, sl + S_RES);
         read_scalars(c, S_RES, 2);
         res[k] = std::sqrt(c->hscal[S_RES]) / nb;
         err[k] = std::sqrt(c->hscal[S_ERR]) / nxt;
@@ -1585,7 +1576,7 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
     }
     if (k == maxit) k = maxit - 1;
     const int nit = k + 1;
-    stage_out_n<T>(c, x_out, x, n, dev, po);
+    stage_out_n<double>(c, x_out, x, n, dev, po);
     if (err_out) std::memcpy(err_out, err.data(), sizeof(double) * nit);
     if (res_out) std::memcpy(res_out, res.data(), sizeof(double) * nit);
     if (niters) *niters = nit;
@@ -1603,55 +1594,39 @@ int arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const double* b_in, 
     (void)n_order(c, A, B);   // H does not depend on the stored pixel order (up to rounding)
     HGM_REQUIRE(A->dtype == HGM_F64, "Arnoldi is fp64");
     HGM_REQUIRE(kg >= 1, "k must be >= 1");
-    using T = double;
     const int64_t m = A->rows, n = A->cols;
     const bool nspace = side == HGM_SIDE_BA;
     const int64_t dim = nspace ? n : m;
     const bool dist = nspace && dist_n(c);
-    const int64_t ldq = krylov_ld(c, dim, dist);
     HGM_REQUIRE(!c->num.parity || !dist_n(c), "parity mode: single rank");
-    const T* b = stage_in<T>(c, "in_b", b_in, m, false);
-    T* Q = c->buf<T>("Q", (size_t)ldq * (kg + 1));
-    if (krylov_padded(c, ldq)) HGM_HIP(hipMemsetAsync(Q, 0, sizeof(T) * ldq * (kg + 1), c->stream));
-    T* Hd = c->buf<T>("H", (size_t)(kg + 1) * kg);
-    T* t = c->buf<T>("t_m", m + 1);
-    T* tn = c->buf<T>("t_n", n + 1);
-    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(T) * (kg + 1) * kg, c->stream));
-    if (nspace) apply_B<T>(c, B, b, Q, EPI_NONE, 0.0, nullptr);                // :8  r0 = B*b
-    else HGM_HIP(hipMemcpyAsync(Q, b, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));   // :5
-    if (nspace) nsumsq<T>(c, dim, Q, dslot<T>(c, S_BETA));
-    else sumsq<T>(c, dim, Q, dslot<T>(c, S_BETA));
-    const double beta = std::sqrt(read1<T>(c, dslot<T>(c, S_BETA)));           // :12
-    div_scalar<T>(c, dim, Q, Q, beta);                                         // :15
+    const double* b = stage_in<double>(c, "in_b", b_in, m, false);
+    const KrylovBasis kb = krylov_basis(c, "Q", dim, kg + 1, dist);
+    double* Q = kb.Q;
+    const int64_t ldq = kb.ld;
+    double* Hd = c->buf<double>("H", (size_t)(kg + 1) * kg);
+    double* t = c->buf<double>("t_m", m + 1);
+    double* tn = c->buf<double>("t_n", n + 1);
+    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(double) * (kg + 1) * kg, c->stream));
+    start_residual(c, B, b, nspace, kb, dslot<double>(c, S_BETA));                 // :5 / :8  r0
+    const double beta = std::sqrt(read1<double>(c, dslot<double>(c, S_BETA)));           // :12
+    div_scalar<double>(c, dim, Q, Q, beta);                                         // :15
     std::vector<double> H((size_t)(kg + 1) * kg, 0.0);
     int done = 0;
-    const FusedPlan* fplan = nullptr;                                          // A*(B*q) in one pass
-    if constexpr (std::is_same_v<T, double>) if (!nspace) fplan = fused_ab_plan(c, A, B);
+    const FusedPlan* fplan = nspace ? nullptr : fused_ab_plan(c, A, B);        // A*(B*q) in one pass
     // The steps are enqueued back to back, with no host round trip per step: the breakdown
     // test H(k+1,k) < btol runs on the host afterwards, and the steps past a breakdown (which
     // wrote only Q(:,>k+1) and H(:,>k) on the device) are discarded.
     for (int k = 0; k < kg; ++k) {
-        T* qk = Q + (int64_t)k * ldq;
-        T* v = Q + (int64_t)(k + 1) * ldq;
-        if (nspace) {
-            apply_A<T>(c, A, qk, t, EPI_NONE, 0.0, nullptr);
-            apply_B<T>(c, B, t, v, EPI_NONE, 0.0, nullptr);                    // :22 B*(A*Q(:,k))
-        } else if (fplan) {
-            if constexpr (std::is_same_v<T, double>) {
-                fused_ab(c, B, fplan, qk, tn, v);                                 // :20
-                if (dist_n(c)) allreduce(c, v, A->rows);
-            }
-        } else {
-            apply_B<T>(c, B, qk, tn, EPI_NONE, 0.0, nullptr);
-            apply_A<T>(c, A, tn, v, EPI_NONE, 0.0, nullptr);                   // :20 A*(B*Q(:,k))
-        }
-        T* Hcol = Hd + (int64_t)k * (kg + 1);
-        if (orth == HGM_CGS2) cgs2<T>(c, dim, Q, ldq, k, Hcol, dist);
-        else mgs<T>(c, dim, Q, ldq, k, Hcol, dist);                            // :25-31
+        double* qk = Q + (int64_t)k * ldq;
+        double* v = Q + (int64_t)(k + 1) * ldq;
+        apply_M(c, A, B, fplan, nspace, qk, nspace ? t : tn, v);      // :22 B*(A*Q(:,k)) / :20 A*(B*Q(:,k))
+        double* Hcol = Hd + (int64_t)k * (kg + 1);
+        if (orth == HGM_CGS2) cgs2<double>(c, dim, Q, ldq, k, Hcol, dist);
+        else mgs<double>(c, dim, Q, ldq, k, Hcol, dist);                            // :25-31
     }
     std::vector<double> Hall((size_t)(kg + 1) * kg);
     Reader rd(c);
-    rd.add(Hall.data(), Hd, sizeof(T) * Hall.size());
+    rd.add(Hall.data(), Hd, sizeof(double) * Hall.size());
     rd.go();
     for (int k = 0; k < kg; ++k) {
         std::memcpy(&H[(size_t)k * (kg + 1)], &Hall[(size_t)k * (kg + 1)], sizeof(double) * (k + 2));
@@ -1697,12 +1672,10 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         HGM_REQUIRE(std::isfinite(lambdas[l]) && lambdas[l] >= 0.0, "lambda sweep: every lambda must be finite and >= 0");
     HGM_REQUIRE(niters != nullptr, "niters is required");
     const PixOrder po = n_order(c, A, B);
-    using T = double;
     const int orth = o ? o->orth : HGM_MGS;
     const int64_t m = A->rows, n = A->cols;
     const bool nspace = side == HGM_SIDE_BA;
     const int64_t dim = nspace ? n : m;
-    const int64_t ldq = krylov_ld(c, dim, false);
     const int64_t ldaq = round_up(m > 0 ? m : 1, 64), ldbq = round_up(n > 0 ? n : 1, 64);
     const double nan = std::numeric_limits<double>::quiet_NaN();
     const size_t surf = (size_t)maxit * nlam;
@@ -1710,81 +1683,71 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     if (res_surf) std::fill(res_surf, res_surf + surf, nan);
     if (sol_surf) std::fill(sol_surf, sol_surf + surf, nan);
 
-    T* Q = c->buf<T>("Q", (size_t)ldq * (maxit + 1));
-    if (krylov_padded(c, ldq)) HGM_HIP(hipMemsetAsync(Q, 0, sizeof(T) * ldq * (maxit + 1), c->stream));
+    const KrylovBasis kb = krylov_basis(c, "Q", dim, maxit + 1, false);
+    double* Q = kb.Q;
+    const int64_t ldq = kb.ld;
     // kept products: BA: W = A*Q ; AB: V = B*Q and W = A*B*Q
-    T* AQ = nspace ? c->buf<T>("AQ", (size_t)ldaq * maxit) : nullptr;
-    T* BQ = nspace ? nullptr : c->buf<T>("BQ", (size_t)ldbq * maxit);
-    T* ABQ = nspace ? nullptr : c->buf<T>("ABQ", (size_t)ldaq * maxit);
-    const T* V = nspace ? Q : BQ;
+    double* AQ = nspace ? c->buf<double>("AQ", (size_t)ldaq * maxit) : nullptr;
+    double* BQ = nspace ? nullptr : c->buf<double>("BQ", (size_t)ldbq * maxit);
+    double* ABQ = nspace ? nullptr : c->buf<double>("ABQ", (size_t)ldaq * maxit);
+    const double* V = nspace ? Q : BQ;
     const int64_t ldv = nspace ? ldq : ldbq;
-    const T* W = nspace ? AQ : ABQ;
-    T* x = c->buf<T>("x", n > 0 ? n : 1);
-    T* Hd = c->buf<T>("H", (size_t)(maxit + 1) * maxit);
+    const double* W = nspace ? AQ : ABQ;
+    double* x = c->buf<double>("x", n > 0 ? n : 1);
+    double* Hd = c->buf<double>("H", (size_t)(maxit + 1) * maxit);
     const int64_t ldy = maxit;
-    T* Yd[2] = {c->buf<T>("sweep_Y0", (size_t)ldy * nlam), c->buf<T>("sweep_Y1", (size_t)ldy * nlam)};
-    T* mon = c->buf<T>("sweep_mon", (size_t)4 * nlam);   // [res^2 | (W y)^2 | err^2 | (V y)^2]
-    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(T) * (maxit + 1) * maxit, c->stream));
-    const T* b = stage_in<T>(c, "in_b", b_in, m, false);
-    const T* xt = stage_in_n<T>(c, "in_xt", xt_in, n, false, po);
+    double* Yd[2] = {c->buf<double>("sweep_Y0", (size_t)ldy * nlam), c->buf<double>("sweep_Y1", (size_t)ldy * nlam)};
+    double* mon = c->buf<double>("sweep_mon", (size_t)4 * nlam);   // [res^2 | (W y)^2 | err^2 | (V y)^2]
+    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(double) * (maxit + 1) * maxit, c->stream));
+    const double* b = stage_in<double>(c, "in_b", b_in, m, false);
+    const double* xt = stage_in_n<double>(c, "in_xt", xt_in, n, false, po);
 
-    sumsq<T>(c, m, b, dslot<T>(c, S_NB));
-    if (xt) sumsq<T>(c, n, xt, dslot<T>(c, S_NXT));
-    // r0 (*_bounds.m:11-13): BA: B*(b - A*0) ; AB: b - A*(B*0)
-    if (nspace) apply_B<T>(c, B, b, Q, EPI_NONE, T(0), nullptr);
-    else HGM_HIP(hipMemcpyAsync(Q, b, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
-    sumsq<T>(c, dim, Q, dslot<T>(c, S_BETA));
+    sumsq<double>(c, m, b, dslot<double>(c, S_NB));
+    if (xt) sumsq<double>(c, n, xt, dslot<double>(c, S_NXT));
+    start_residual(c, B, b, nspace, kb, dslot<double>(c, S_BETA));           // r0 (*_bounds.m:11-13)
     read_scalars(c, 0, 3);
     const double nb = std::sqrt(c->hscal[S_NB]);
     const double nxt = xt ? std::sqrt(c->hscal[S_NXT]) : 0.0;
     const double beta = std::sqrt(c->hscal[S_BETA]);
-    div_scalar<T>(c, dim, Q, Q, (T)beta);
+    div_scalar<double>(c, dim, Q, Q, beta);
 
     const FusedPlan* fplan = nspace ? nullptr : fused_ab_plan(c, A, B);
     std::vector<double> H((size_t)(maxit + 1) * maxit, 0.0);
     auto Hh = [&](int i, int j) -> double& { return H[(size_t)j * (maxit + 1) + i]; };
     std::vector<char> active(nlam, 1);
     int nactive = nlam;
-    std::vector<double> Yh((size_t)ldy * nlam), G, M, rhs, y, mh((size_t)4 * nlam);
+    std::vector<double> Yh((size_t)ldy * nlam), G, mh((size_t)4 * nlam);
     // lambda l stops with iterate kx (0-based iteration; -1: x never assigned) after nit iterations
     auto finish = [&](int l, int nit, int kx) {
         active[l] = 0;
         --nactive;
         niters[l] = nit;
         if (X_out == nullptr || kx < 0) return;
-        gemv<T>(c, n, kx + 1, V, ldv, Yd[kx & 1] + (size_t)l * ldy, x, 0);      // :37-38  x = V_k y
-        stage_out_n<T>(c, X_out + (size_t)l * n, x, n, false, po);
+        gemv<double>(c, n, kx + 1, V, ldv, Yd[kx & 1] + (size_t)l * ldy, x, 0);      // :37-38  x = V_k y
+        stage_out_n<double>(c, X_out + (size_t)l * n, x, n, false, po);
     };
     int k = 0;
     bool unassigned = false;
     for (k = 0; k < maxit && nactive > 0; ++k) {
-        T* qk = Q + (int64_t)k * ldq;
-        T* v = Q + (int64_t)(k + 1) * ldq;
-        const T* src = nullptr;                                  // the vector the sweep orthogonalises
+        double* qk = Q + (int64_t)k * ldq;
+        double* v = Q + (int64_t)(k + 1) * ldq;
+        const double* src = nullptr;                                  // the vector the sweep orthogonalises
         // ---- operator (*_bounds.m:25) ----
         if (nspace) {
-            T* Aq = AQ + (int64_t)k * ldaq;
-            apply_A<T>(c, A, qk, Aq, EPI_NONE, T(0), nullptr);
-            apply_B<T>(c, B, Aq, v, EPI_NONE, T(0), nullptr);
+            apply_M(c, A, B, nullptr, true, qk, AQ + (int64_t)k * ldaq, v);
         } else {
-            T* Bq = BQ + (int64_t)k * ldbq;
-            T* w = ABQ + (int64_t)k * ldaq;
-            if (fplan) {
-                fused_ab(c, B, fplan, qk, Bq, w);
-            } else {
-                apply_B<T>(c, B, qk, Bq, EPI_NONE, T(0), nullptr);
-                apply_A<T>(c, A, Bq, w, EPI_NONE, T(0), nullptr);
-            }
+            double* w = ABQ + (int64_t)k * ldaq;
+            apply_M(c, A, B, fplan, false, qk, BQ + (int64_t)k * ldbq, w);
             if (orth == HGM_CGS2)
-                HGM_HIP(hipMemcpyAsync(v, w, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+                HGM_HIP(hipMemcpyAsync(v, w, sizeof(double) * m, hipMemcpyDeviceToDevice, c->stream));
             else src = w;
         }
         // ---- orthogonalisation (:26-32) ----
-        T* Hcol = Hd + (int64_t)k * (maxit + 1);
-        if (orth == HGM_CGS2) cgs2<T>(c, dim, Q, ldq, k, Hcol, false);
-        else mgs<T>(c, dim, Q, ldq, k, Hcol, false, src);
+        double* Hcol = Hd + (int64_t)k * (maxit + 1);
+        if (orth == HGM_CGS2) cgs2<double>(c, dim, Q, ldq, k, Hcol, false);
+        else mgs<double>(c, dim, Q, ldq, k, Hcol, false, src);
         Reader rd(c);
-        rd.add(&Hh(0, k), Hcol, sizeof(T) * (k + 2));
+        rd.add(&Hh(0, k), Hcol, sizeof(double) * (k + 2));
         rd.go();
         if (Hh(k + 1, k) == 0) {                                 // :31  breakdown: every lambda stops here
             if (k == 0) unassigned = true;
@@ -1803,30 +1766,17 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         // ---- projected solves (:34-36), one per running lambda; Hk'*Hk and Hk'*tk are shared ----
         const int kk = k + 1;
         G.assign((size_t)kk * kk, 0.0);
-        for (int i = 0; i < kk; ++i)
-            for (int j = 0; j < kk; ++j) {
-                double s = 0;
-                for (int r = 0; r <= kk; ++r) s += Hh(r, i) * Hh(r, j);
-                G[(size_t)j * kk + i] = s;
-            }
-        rhs.assign(kk, 0.0);
-        for (int i = 0; i < kk; ++i) rhs[i] = Hh(0, i) * beta;
-        y.assign(kk, 0.0);
+        dense::normal_matrix(H.data(), maxit + 1, kk, G.data());
         std::fill(Yh.begin(), Yh.end(), 0.0);
-        for (int l = 0; l < nlam; ++l) {
-            if (!active[l]) continue;
-            M = G;
-            for (int i = 0; i < kk; ++i) M[(size_t)i * kk + i] = G[(size_t)i * kk + i] + lambdas[l];
-            dense::mldivide_square(kk, M.data(), rhs.data(), y.data());
-            std::memcpy(&Yh[(size_t)l * ldy], y.data(), sizeof(double) * kk);
-        }
-        T* Yk = Yd[k & 1];
-        h2d(c, Yk, Yh.data(), sizeof(T) * Yh.size());
+        for (int l = 0; l < nlam; ++l)
+            if (active[l]) dense::proj_ptr(G.data(), H.data(), maxit + 1, kk, beta, lambdas[l], &Yh[(size_t)l * ldy]);
+        double* Yk = Yd[k & 1];
+        h2d(c, Yk, Yh.data(), sizeof(double) * Yh.size());
         // ---- monitors of every lambda (:37-41): two passes over the kept products ----
-        proj_norms<T>(c, m, kk, W, ldaq, Yk, ldy, nlam, b, mon, mon + nlam);
-        proj_norms<T>(c, n, kk, V, ldv, Yk, ldy, nlam, xt, mon + 2 * nlam, mon + 3 * nlam);
+        proj_norms<double>(c, m, kk, W, ldaq, Yk, ldy, nlam, b, mon, mon + nlam);
+        proj_norms<double>(c, n, kk, V, ldv, Yk, ldy, nlam, xt, mon + 2 * nlam, mon + 3 * nlam);
         Reader rm(c);
-        rm.add(mh.data(), mon, sizeof(T) * 4 * nlam);
+        rm.add(mh.data(), mon, sizeof(double) * 4 * nlam);
         rm.go();
         for (int l = 0; l < nlam; ++l) {
             if (!active[l]) continue;
@@ -1886,13 +1836,10 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                         "batched solve: every lambda must be finite and >= 0");
     }
     const PixOrder po = n_order(c, A, B);
-    using T = double;
     const int orth = o ? o->orth : HGM_MGS;
     const bool nspace = side == HGM_SIDE_BA;
     const int64_t dim = nspace ? n : m;
-    const int64_t ldq = krylov_ld(c, dim, false);
     const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
-    const size_t qs = (size_t)ldq * (maxit + 1);            // one column's basis
     const size_t hs = (size_t)(maxit + 1) * maxit;           // one column's Hessenberg
     const double nan = std::numeric_limits<double>::quiet_NaN();
     if (err_hist) std::fill(err_hist, err_hist + (size_t)maxit * nrhs, nan);
@@ -1901,44 +1848,46 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     if (col_status) std::fill(col_status, col_status + nrhs, (int)HGM_OK);
 
     // ---- device storage: every per-column array is one slab with a constant column stride ----
-    T* Qall = c->buf<T>("bt_Q", qs * nrhs);
-    if (krylov_padded(c, ldq)) HGM_HIP(hipMemsetAsync(Qall, 0, sizeof(T) * qs * nrhs, c->stream));
+    const KrylovBasis kb = krylov_basis(c, "bt_Q", dim, (maxit + 1) * nrhs, false);
+    double* Qall = kb.Q;
+    const int64_t ldq = kb.ld;
+    const size_t qs = (size_t)ldq * (maxit + 1);            // one column's basis
     // kept products: BA: W = A*Q ; AB: V = B*Q and W = A*B*Q  (the sweep's, per column)
-    T* Wall = c->buf<T>("bt_W", (size_t)ldm * maxit * nrhs);
-    T* Vall = nspace ? nullptr : c->buf<T>("bt_V", (size_t)ldn * maxit * nrhs);
-    T* ball = c->buf<T>("bt_b", (size_t)ldm * nrhs);
+    double* Wall = c->buf<double>("bt_W", (size_t)ldm * maxit * nrhs);
+    double* Vall = nspace ? nullptr : c->buf<double>("bt_V", (size_t)ldn * maxit * nrhs);
+    double* ball = c->buf<double>("bt_b", (size_t)ldm * nrhs);
     const int nxt_cols = xt_in ? (ldxt == 0 ? 1 : nrhs) : 1;
-    T* xtall = c->buf<T>("bt_xt", (size_t)ldn * nxt_cols);
-    T* xall = c->buf<T>("bt_x", (size_t)ldn * nrhs);
-    T* Hd = c->buf<T>("bt_H", hs * nrhs);
-    T* Yd = c->buf<T>("bt_y", (size_t)maxit * nrhs);
-    T* mon = c->buf<T>("bt_mon", (size_t)2 * nrhs);          // [res^2, err^2] per column
-    T* scal = c->buf<T>("bt_scal", (size_t)3 * nrhs);        // [||b||^2, ||x_true||^2, ||r0||^2] per column
+    double* xtall = c->buf<double>("bt_xt", (size_t)ldn * nxt_cols);
+    double* xall = c->buf<double>("bt_x", (size_t)ldn * nrhs);
+    double* Hd = c->buf<double>("bt_H", hs * nrhs);
+    double* Yd = c->buf<double>("bt_y", (size_t)maxit * nrhs);
+    double* mon = c->buf<double>("bt_mon", (size_t)2 * nrhs);          // [res^2, err^2] per column
+    double* scal = c->buf<double>("bt_scal", (size_t)3 * nrhs);        // [||b||^2, ||x_true||^2, ||r0||^2] per column
     // interleaved multi-vectors of the operator passes (two per space: source and product)
-    T* Im[2] = {c->buf<T>("bt_im0", (size_t)(m > 0 ? m : 1) * SPMM_MAXV),
-                c->buf<T>("bt_im1", (size_t)(m > 0 ? m : 1) * SPMM_MAXV)};
-    T* In[2] = {c->buf<T>("bt_in0", (size_t)(n > 0 ? n : 1) * SPMM_MAXV),
-                c->buf<T>("bt_in1", (size_t)(n > 0 ? n : 1) * SPMM_MAXV)};
-    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(T) * hs * nrhs, c->stream));
+    double* Im[2] = {c->buf<double>("bt_im0", (size_t)(m > 0 ? m : 1) * SPMM_MAXV),
+                c->buf<double>("bt_im1", (size_t)(m > 0 ? m : 1) * SPMM_MAXV)};
+    double* In[2] = {c->buf<double>("bt_in0", (size_t)(n > 0 ? n : 1) * SPMM_MAXV),
+                c->buf<double>("bt_in1", (size_t)(n > 0 ? n : 1) * SPMM_MAXV)};
+    HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(double) * hs * nrhs, c->stream));
     auto Qj = [&](int j) { return Qall + qs * (size_t)j; };
     auto Wj = [&](int j) { return Wall + (size_t)ldm * maxit * j; };
-    auto Vj = [&](int j) -> const T* { return nspace ? Qj(j) : Vall + (size_t)ldn * maxit * j; };
+    auto Vj = [&](int j) -> const double* { return nspace ? Qj(j) : Vall + (size_t)ldn * maxit * j; };
     const int64_t ldv = nspace ? ldq : ldn;
     auto bj = [&](int j) { return ball + (size_t)ldm * j; };
-    auto xtj = [&](int j) -> const T* { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
+    auto xtj = [&](int j) -> const double* { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
     auto xj = [&](int j) { return xall + (size_t)ldn * j; };
 
-    for (int j = 0; j < nrhs; ++j) h2d(c, bj(j), Bm + (size_t)ldb * j, sizeof(T) * m);
+    for (int j = 0; j < nrhs; ++j) h2d(c, bj(j), Bm + (size_t)ldb * j, sizeof(double) * m);
     if (xt_in) {
         // x_true in the reference order, permuted into the operators' stored pixel order
-        T* tmp = po.trivial() ? nullptr : c->buf<T>("bt_xt_ref", n > 0 ? n : 1);
+        double* tmp = po.trivial() ? nullptr : c->buf<double>("bt_xt_ref", n > 0 ? n : 1);
         for (int j = 0; j < nxt_cols; ++j) {
-            T* dst = xtall + (size_t)ldn * j;
-            h2d(c, po.trivial() ? dst : tmp, xt_in + (size_t)ldxt * j, sizeof(T) * n);
-            if (!po.trivial()) pix_permute<T>(c, po, tmp, dst, 0);
+            double* dst = xtall + (size_t)ldn * j;
+            h2d(c, po.trivial() ? dst : tmp, xt_in + (size_t)ldxt * j, sizeof(double) * n);
+            if (!po.trivial()) pix_permute<double>(c, po, tmp, dst, 0);
         }
     } else {
-        HGM_HIP(hipMemsetAsync(xtall, 0, sizeof(T) * ldn, c->stream));   // the monitor's operand; errors stay NaN
+        HGM_HIP(hipMemsetAsync(xtall, 0, sizeof(double) * ldn, c->stream));   // the monitor's operand; errors stay NaN
     }
 
     // per-column scratch of the orthogonalisation: the one-reduction MGS keeps its Gram triangle in a
@@ -1956,7 +1905,7 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         for (int r = 0; r < SPMM_MAXV; ++r) ts.p[r] = tm.p[r] = td.p[r] = nullptr;
         for (int r = 0; r < nv; ++r) {
             const int j = cols[g0 + r];
-            ts.p[r] = const_cast<T*>(src(j));
+            ts.p[r] = const_cast<double*>(src(j));
             tm.p[r] = mid(j);
             td.p[r] = dst(j);
         }
@@ -1964,14 +1913,14 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         timing_begin(c, KC_SPMM, &tev);
         // first: cols(first) -> rows(first) ; second: rows(first) = cols(second) -> rows(second)
         const bool from_m = first == B;                          // B maps the ray space to the pixel space
-        T* I0 = from_m ? Im[0] : In[0];
-        T* I1 = from_m ? In[0] : Im[0];
+        double* I0 = from_m ? Im[0] : In[0];
+        double* I1 = from_m ? In[0] : Im[0];
         mv_pack(c, first->cols, nv, ts, I0);
         spmm(c, first, nv, I0, I1);
         if (tm.p[0]) mv_unpack(c, first->rows, nv, I1, tm);
         double bytes = 12.0 * first->nnz + 8.0 * spmm_width(nv) * (first->rows + first->cols);
         if (second) {
-            T* I2 = from_m ? Im[1] : In[1];
+            double* I2 = from_m ? Im[1] : In[1];
             spmm(c, second, nv, I1, I2);
             mv_unpack(c, second->rows, nv, I2, td);
             bytes += 12.0 * second->nnz + 8.0 * spmm_width(nv) * (second->rows + second->cols);
@@ -1985,22 +1934,22 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     if (nspace) {
         for (size_t g0 = 0; g0 < act.size(); g0 += SPMM_MAXV) {
             const int nv = (int)std::min<size_t>(SPMM_MAXV, act.size() - g0);
-            operator_pass(act, g0, nv, B, nullptr, [&](int j) { return (const T*)bj(j); },
-                          [&](int j) { return Qj(j); }, [&](int) { return (T*)nullptr; });
+            operator_pass(act, g0, nv, B, nullptr, [&](int j) { return (const double*)bj(j); },
+                          [&](int j) { return Qj(j); }, [&](int) { return (double*)nullptr; });
         }
     } else {
         for (int j = 0; j < nrhs; ++j)
-            HGM_HIP(hipMemcpyAsync(Qj(j), bj(j), sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+            HGM_HIP(hipMemcpyAsync(Qj(j), bj(j), sizeof(double) * m, hipMemcpyDeviceToDevice, c->stream));
     }
     for (int j = 0; j < nrhs; ++j) {
-        sumsq<T>(c, m, bj(j), scal + 3 * j);
-        if (xt_in) sumsq<T>(c, n, xtj(j), scal + 3 * j + 1);
-        sumsq<T>(c, dim, Qj(j), scal + 3 * j + 2);
+        sumsq<double>(c, m, bj(j), scal + 3 * j);
+        if (xt_in) sumsq<double>(c, n, xtj(j), scal + 3 * j + 1);
+        sumsq<double>(c, dim, Qj(j), scal + 3 * j + 2);
     }
     std::vector<double> sh((size_t)3 * nrhs, 0.0);
     {
         Reader rd(c);
-        rd.add(sh.data(), scal, sizeof(T) * 3 * nrhs);
+        rd.add(sh.data(), scal, sizeof(double) * 3 * nrhs);
         rd.go();
     }
     std::vector<double> nb(nrhs), nxt(nrhs), beta(nrhs);
@@ -2008,46 +1957,48 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         nb[j] = std::sqrt(sh[3 * (size_t)j]);
         nxt[j] = xt_in ? std::sqrt(sh[3 * (size_t)j + 1]) : 0.0;
         beta[j] = std::sqrt(sh[3 * (size_t)j + 2]);
-        div_scalar<T>(c, dim, Qj(j), Qj(j), (T)beta[j]);      // :13  Q(:,1) = r0 / beta
+        div_scalar<double>(c, dim, Qj(j), Qj(j), beta[j]);      // :13  Q(:,1) = r0 / beta
     }
 
     std::vector<double> H(hs * nrhs, 0.0);
     auto Hh = [&](int j, int i, int k) -> double& { return H[hs * (size_t)j + (size_t)k * (maxit + 1) + i]; };
     std::vector<char> x_assigned(nrhs, 0);
-    std::vector<double> Yh((size_t)maxit * nrhs, 0.0), mh((size_t)2 * nrhs, 0.0), y, rhs, M;
+    std::vector<double> Yh((size_t)maxit * nrhs, 0.0), mh((size_t)2 * nrhs, 0.0), M;
     std::vector<int> next, ran;
     bool unassigned = false;
     for (int k = 0; k < maxit && !act.empty(); ++k) {
         // ---- operator (*_bounds.m:25) over the running columns, repacked in groups of at most 8 ----
         for (size_t g0 = 0; g0 < act.size(); g0 += SPMM_MAXV) {
             const int nv = (int)std::min<size_t>(SPMM_MAXV, act.size() - g0);
-            auto qk = [&](int j) { return (const T*)(Qj(j) + (int64_t)k * ldq); };
+            auto qk = [&](int j) { return (const double*)(Qj(j) + (int64_t)k * ldq); };
             if (nspace)    // A*q kept, B*(A*q) is the new basis vector
                 operator_pass(act, g0, nv, A, B, qk, [&](int j) { return Wj(j) + (int64_t)k * ldm; },
                               [&](int j) { return Qj(j) + (int64_t)(k + 1) * ldq; });
             else           // B*q and A*(B*q) kept; the latter is orthogonalised into the new basis vector
                 operator_pass(act, g0, nv, B, A, qk,
-                              [&](int j) { return const_cast<T*>(Vj(j)) + (int64_t)k * ldn; },
+                              [&](int j) { return const_cast<double*>(Vj(j)) + (int64_t)k * ldn; },
                               [&](int j) { return Wj(j) + (int64_t)k * ldm; });
         }
         // ---- orthogonalisation (:26-32), the single solver's sweep once per running column ----
         for (int j : act) {
             ColTag tag(c, j);
-            T* Q = Qj(j);
-            T* v = Q + (int64_t)(k + 1) * ldq;
-            const T* src = nullptr;
+            double* Q = Qj(j);
+            double* v = Q + (int64_t)(k + 1) * ldq;
+            const double* src = nullptr;
             if (!nspace) {
-                const T* w = Wj(j) + (int64_t)k * ldm;
-                if (orth == HGM_CGS2) HGM_HIP(hipMemcpyAsync(v, w, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
+                const double* w = Wj(j) + (int64_t)k * ldm;
+                if (orth == HGM_CGS2)
+                    HGM_HIP(hipMemcpyAsync(v, w, sizeof(double) * m, hipMemcpyDeviceToDevice, c->stream));
                 else src = w;
             }
-            T* Hcol = Hd + hs * (size_t)j + (size_t)k * (maxit + 1);
-            if (orth == HGM_CGS2) cgs2<T>(c, dim, Q, ldq, k, Hcol, false);
-            else mgs<T>(c, dim, Q, ldq, k, Hcol, false, src);
+            double* Hcol = Hd + hs * (size_t)j + (size_t)k * (maxit + 1);
+            if (orth == HGM_CGS2) cgs2<double>(c, dim, Q, ldq, k, Hcol, false);
+            else mgs<double>(c, dim, Q, ldq, k, Hcol, false, src);
         }
         {
             Reader rd(c);
-            for (int j : act) rd.add(&Hh(j, 0, k), Hd + hs * (size_t)j + (size_t)k * (maxit + 1), sizeof(T) * (k + 2));
+            for (int j : act)
+                rd.add(&Hh(j, 0, k), Hd + hs * (size_t)j + (size_t)k * (maxit + 1), sizeof(double) * (k + 2));
             rd.go();
         }
         // ---- projected solves (:34-36) on the host, per column ----
@@ -2067,41 +2018,27 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                 }
                 continue;
             }
-            y.assign(kk, 0.0);
+            const double* Hj = &Hh(j, 0, 0);
+            double* y = &Yh[(size_t)j * maxit];
             if (!hybrid) {
-                // yk = H(1:k+1,1:k) \ [beta; zeros(k,1)]   (*_nonhybrid_bounds.m:34-36)
-                M.assign((size_t)(kk + 1) * kk, 0.0);
-                for (int jj = 0; jj < kk; ++jj)
-                    for (int i = 0; i <= kk; ++i) M[(size_t)jj * (kk + 1) + i] = Hh(j, i, jj);
-                rhs.assign(kk + 1, 0.0);
-                rhs[0] = beta[j];
-                dense::qr_ls(kk + 1, kk, M.data(), rhs.data(), y.data());
+                dense::proj_ls(Hj, maxit + 1, kk, beta[j], y);
             } else {
-                // yk = (Hk'*Hk + lambda*eye(k)) \ (Hk'*tk)   (*_hybrid_bounds.m:34-36)
                 M.assign((size_t)kk * kk, 0.0);
-                for (int i = 0; i < kk; ++i)
-                    for (int jj = 0; jj < kk; ++jj) {
-                        double s = 0;
-                        for (int r = 0; r <= kk; ++r) s += Hh(j, r, i) * Hh(j, r, jj);
-                        M[(size_t)jj * kk + i] = s + (i == jj ? lambdas[j] : 0.0);
-                    }
-                rhs.assign(kk, 0.0);
-                for (int i = 0; i < kk; ++i) rhs[i] = Hh(j, 0, i) * beta[j];
-                dense::mldivide_square(kk, M.data(), rhs.data(), y.data());
+                dense::normal_matrix(Hj, maxit + 1, kk, M.data());
+                dense::proj_ptr(M.data(), Hj, maxit + 1, kk, beta[j], lambdas[j], y);
             }
-            std::memcpy(&Yh[(size_t)j * maxit], y.data(), sizeof(double) * kk);
             ran.push_back(j);
         }
         // ---- monitors (:37-41) from the kept products: x = V_k y, ||x - x_true||^2, ||b - W_k y||^2 ----
         if (!ran.empty()) {
-            h2d(c, Yd, Yh.data(), sizeof(T) * Yh.size());
+            h2d(c, Yd, Yh.data(), sizeof(double) * Yh.size());
             for (int j : ran) {
-                recon<T>(c, n, kk, Vj(j), ldv, Yd + (size_t)j * maxit, xj(j), xtj(j), mon + 2 * j + 1, m, Wj(j), ldm,
-                         bj(j), mon + 2 * j);
+                recon<double>(c, n, kk, Vj(j), ldv, Yd + (size_t)j * maxit, xj(j), xtj(j), mon + 2 * j + 1, m, Wj(j),
+                              ldm, bj(j), mon + 2 * j);
                 x_assigned[j] = 1;
             }
             Reader rm(c);
-            rm.add(mh.data(), mon, sizeof(T) * 2 * nrhs);
+            rm.add(mh.data(), mon, sizeof(double) * 2 * nrhs);
             rm.go();
         }
         for (int j : ran) {
@@ -2115,7 +2052,7 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     }
     if (X_out)
         for (int j = 0; j < nrhs; ++j)
-            if (x_assigned[j]) stage_out_n<T>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
+            if (x_assigned[j]) stage_out_n<double>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
     if (o && o->H_out) std::memcpy(o->H_out, H.data(), sizeof(double) * H.size());
     if (unassigned)
         throw Error{HGM_E_NOT_ASSIGNED, "Output argument \"x\" not assigned in at least one column (breakdown at k = 1)"};

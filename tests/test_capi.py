@@ -60,6 +60,22 @@ def test_gcv_from_H_host_code_matches_oracle(H_case):
         assert abs(g - gr) <= 1e-10 * abs(gr)
 
 
+def test_gcv_from_H_smallest_projected_systems(H_case):
+    """k = 1, 2 and 7 on the leading blocks of the fixture's H (leading dimension k + 1, not the
+    fixture's 11): the sizes at which an indexing slip in the shared normal-matrix / projected-solve
+    helpers (ldh against k, the r <= k row bound) would show.  lambda = 0 and a huge lambda stay finite."""
+    P, H, beta = H_case
+    n = P.A.shape[1]
+    for k in (1, 2, 7):
+        Hk = np.ascontiguousarray(H[:k + 1, :k])
+        for lam in (1e-8, 1e-5, 1e-3, 1e-1):
+            g = hgmres.gcv_from_H(Hk, beta, lam, n)
+            gr = R.gcv_from_H(Hk, beta, lam, n)
+            assert abs(g - gr) <= 1e-10 * abs(gr), (k, lam, g, gr)
+        for lam in (0.0, 1e12):
+            assert np.isfinite(hgmres.gcv_from_H(Hk, beta, lam, n)), (k, lam)
+
+
 def test_gcv_fallback_value(H_case):
     # singular projected system -> NaN -> 1e20 (gcv_function.m:56-57), as the oracle
     P, H, beta = H_case
