@@ -3,6 +3,8 @@
 
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "internal.h"
 
 namespace hgm {
@@ -116,6 +118,53 @@ __device__ __forceinline__ T reduce_parts(const T* __restrict__ p, int np, T* sh
     for (int i = threadIdx.x; i < np; i += BS) a += p[i];
     return block_sum_all<T, REUSE>(a, sh);
 }
+
+// Grid-stride order of the elementwise kernels with a fused partial sum (VEC: 16-byte vectors of W
+// elements -- thread g of the grid takes vectors g, g + G, ... and their elements in order, and the
+// last block's thread 0 then the n mod W tail; else single elements g, g + G, ...).  Every kernel
+// whose partials must give the same bits as another's (k_lsqr_step's error sum and
+// k_reduce_partial<T, 2>) walks its elements through this.
+template <typename T, bool VEC, typename F>
+__device__ __forceinline__ void grid_elems(int64_t n, F&& f) {
+    if constexpr (VEC) {
+        using V = typename V16<T>::t;
+        constexpr int W = V16<T>::W;
+        (void)sizeof(V);
+        const int64_t nv = n / W;
+#pragma unroll 2
+        for (int64_t g = (int64_t)blockIdx.x * BS + threadIdx.x; g < nv; g += (int64_t)gridDim.x * BS)
+            f(g * W, std::integral_constant<int, W>{});
+        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
+            for (int64_t i = nv * W; i < n; ++i) f(i, std::integral_constant<int, 1>{});
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS)
+            f(i, std::integral_constant<int, 1>{});
+    }
+}
+
+// W consecutive elements from p + i (one 16-byte access for W > 1; i a multiple of W)
+template <int W, typename T>
+__device__ __forceinline__ void vload(const T* p, int64_t i, T (&o)[W]) {
+    if constexpr (W == 1) {
+        o[0] = p[i];
+    } else {
+        const typename V16<T>::t v = *reinterpret_cast<const typename V16<T>::t*>(p + i);
+#pragma unroll
+        for (int e = 0; e < W; ++e) o[e] = v[e];
+    }
+}
+template <int W, typename T>
+__device__ __forceinline__ void vstore(T* p, int64_t i, const T (&o)[W]) {
+    if constexpr (W == 1) {
+        p[i] = o[0];
+    } else {
+        typename V16<T>::t v;
+#pragma unroll
+        for (int e = 0; e < W; ++e) v[e] = o[e];
+        *reinterpret_cast<typename V16<T>::t*>(p + i) = v;
+    }
+}
+
 
 // Fused epilogues of the reference's operator closures, two roundings each (the
 // library is compiled with -ffp-contract=off): t + a*z, t - a*z, z - t.
@@ -249,6 +298,48 @@ static inline void launch(hgm_ctx* c, bool last, void (*kern)(KArgs...), dim3 gr
     } else {
         hipLaunchKernelGGL(kern, grid, block, 0, c->stream, static_cast<KArgs>(args)...);
     }
+}
+
+constexpr int64_t SINGLE_MAX = 1 << 15;   // vectors up to 32 Ki entries: one launch (reduce_to)
+
+// Host side of an elementwise kernel over grid_elems that also leaves one partial sum per block.
+// SUM_LONG: the sum is fused for n > SINGLE_MAX outside parity mode, in k_reduce_partial's layout
+// (parts_for(n) blocks); a shorter vector or a parity solve gets parts == nullptr on a grid_for(n)
+// grid and the caller's separate sumsq / sumsq_diff (reduce_to's single launch, the fixed order).
+// SUM_ANY: fused at any n.  SUM_NONE: no sum wanted.  vec: every pointer is 16-byte aligned (NULL is).
+// lsmr_step and lsmr_step_mon did not test parity before they shared this: they run only on the
+// one-pass plan, which agreed_gk_plan refuses a parity solve, so the term changes nothing there.
+enum SumFuse { SUM_NONE, SUM_LONG, SUM_ANY };
+struct SumPlan {
+    bool fuse, vec;
+    int np;
+};
+template <typename... Ptrs>
+static inline SumPlan sum_plan(const hgm_ctx* c, int64_t n, SumFuse when, Ptrs... ptrs) {
+    SumPlan s;
+    s.fuse = when == SUM_ANY || (when == SUM_LONG && n > SINGLE_MAX && !c->num.parity);
+    s.np = s.fuse ? parts_for(n) : grid_for(n);
+    s.vec = (al16(ptrs) && ...);
+    return s;
+}
+template <typename P>
+struct SumParts {
+    bool fuse;
+    int np;
+    P* parts;
+};
+// Plans, calls kern(VEC as std::bool_constant, np, parts) and, with out, sums the partials into
+// *out (k_finalize).  out == nullptr: the caller's next kernel re-forms the sum from the partials.
+template <typename P, typename K, typename... Ptrs>
+static inline SumParts<P> launch_sum(hgm_ctx* c, int64_t n, SumFuse when, const char* parts_buf, P* out, K&& kern,
+                                     Ptrs... ptrs) {
+    const SumPlan s = sum_plan(c, n, when, ptrs...);
+    P* parts = s.fuse ? c->buf<P>(parts_buf, MAX_PARTS) : nullptr;
+    if (s.vec) kern(std::true_type{}, s.np, parts);
+    else kern(std::false_type{}, s.np, parts);
+    if (s.fuse && out) finalize_parts<P>(c, parts, s.np, out);
+    HGM_HIP(hipGetLastError());
+    return {s.fuse, s.np, parts};
 }
 
 }  // namespace hgm

@@ -278,7 +278,7 @@ inline int64_t stream_chunks(int64_t nnz) { return (nnz + SCH - 1) / SCH; }
 
 namespace hgm {
 
-// ---------------- kernels (kernels.hip) ----------------
+// ---------------- kernels (kernels.hip; the Golub-Kahan ones gk.hip) ----------------
 enum Epi { EPI_NONE = 0, EPI_ADD = 1, EPI_SUB = 2, EPI_RSUB = 3, EPI_DIVH = 4, EPI_ADDQ = 5 };
 
 // Pending normalisation of the Krylov vector (gmres_family): Q(:,k) holds
@@ -316,6 +316,8 @@ int parts_for(int64_t n);
 template <typename T> void dot(hgm_ctx* c, int64_t n, const T* a, const T* b, T* out_dev);
 template <typename T> void sumsq(hgm_ctx* c, int64_t n, const T* a, T* out_dev);
 template <typename T> void sumsq_diff(hgm_ctx* c, int64_t n, const T* a, const T* b, T* out_dev);
+// *out_dev = sum of np block partials (k_finalize: the fixed order every fused partial sum ends in)
+template <typename T> void finalize_parts(hgm_ctx* c, const T* parts, int np, T* out_dev);
 // out[j] = Q(:,j)' * w, j < ncols (local)
 template <typename T>
 void multidot(hgm_ctx* c, int64_t n, int ncols, const T* Q, int64_t ldq, const T* w, T* out_dev,
@@ -401,7 +403,66 @@ template <typename T> void div_scalar(hgm_ctx* c, int64_t n, const T* in, T* out
 // v = v / norm(v) on the device, *nrm_out = norm(v) (system-scope store, e.g. the host ring)
 template <typename T> void normalize_to(hgm_ctx* c, int64_t n, T* v, T* nrm_out);
 template <typename T> void lsqr_update(hgm_ctx* c, int64_t n, T* x, T* w, const T* v, T a, T b);
-// Device-resident LSQR scalars (kernels.hip): the Givens rotation from the sums of squares *ssb
+
+// The Golub-Kahan solvers' rotations, stated once for the host loops (solvers.cpp) and the one-thread
+// kernels (gk.hip k_lsqr_rot / k_lsmr_rot).  Every file of the library is compiled as HIP with
+// -ffp-contract=off, so both sides round each operation on its own.
+// lsqr_solver.m:31-38 from beta (:23) and alpha (:27): updates rho_bar and phi_bar; c_x = phi/rho
+// and c_w = theta/rho are the coefficients of :40-41.  (sqrt is correctly rounded on both sides:
+// the host and the device give the same bits.)
+__host__ __device__ inline void lsqr_rotate(double beta, double alpha, double& rho_bar, double& phi_bar, double& c_x,
+                                            double& c_w) {
+    const double rho = sqrt(rho_bar * rho_bar + beta * beta);   // :31
+    const double cs = rho_bar / rho;                            // :32
+    const double sn = beta / rho;                               // :33
+    const double theta = sn * alpha;                            // :34
+    rho_bar = -cs * alpha;                                      // :35
+    const double phi = cs * phi_bar;                            // :37
+    phi_bar = sn * phi_bar;                                     // :38
+    c_x = phi / rho;                                            // :40
+    c_w = theta / rho;                                          // :41
+}
+// lsmr_solver.m:42-67 from beta (:35) and alpha (:39) of this step.  st = [alpha_k, alphabar, rho,
+// rhobar, cbar, sbar, zetabar, theta/rho of the previous :67, (the device loop's stop slot)];
+// coef = [c_hbar, c_x, c_h] of :64 / :66 / :67; cfm / cfn = the kept-product monitors' coefficients
+// [c1, c0, f, e, cx] (lsmr_monitor) in the m-space (image of v = A*v_k) and the n-space
+// (beta A'u_{k+1} + alpha_k A'u_k).  (The device's hypot and the host's may differ in the last bit.)
+__host__ __device__ inline void lsmr_rotate(double beta, double alpha, double* st, double* coef, double* cfm,
+                                            double* cfn) {
+    const double alpha_k = st[0];
+    const double alphahat = st[1];                                        // :42
+    const double rhoold = st[2];                                          // :43
+    const double rho = hypot(alphahat, beta);                             // :44
+    const double cc = alphahat / rho, ss = beta / rho;                    // :45-46
+    const double thetanew = ss * alpha;                                   // :48
+    st[1] = cc * alpha;                                                   // :49 alphabar
+    const double rhobarold = st[3];                                       // :51
+    const double thetabar = st[5] * rho;                                  // :52
+    const double cr = st[4] * rho;
+    const double rhobar = hypot(cr, thetanew);                            // :53
+    st[4] = cr / rhobar;                                                  // :54 cbar
+    st[5] = thetanew / rhobar;                                            // :55 sbar
+    const double zeta = st[4] * st[6];                                    // :58
+    st[6] = -st[5] * st[6];                                               // :59 zetabar
+    const double c_hbar = (thetabar * rho) / (rhoold * rhobarold);        // :64
+    const double c_x = zeta / (rho * rhobar);                             // :66
+    const double c_h = thetanew / rho;                                    // :67
+    coef[0] = c_hbar;
+    coef[1] = c_x;
+    coef[2] = c_h;
+    const double f = st[7];
+    const double m5[5] = {1.0, 0.0, f, c_hbar, c_x}, n5[5] = {beta, alpha_k, f, c_hbar, c_x};
+    for (int i = 0; i < 5; ++i) {
+        cfm[i] = m5[i];
+        cfn[i] = n5[i];
+    }
+    st[0] = alpha;
+    st[2] = rho;
+    st[3] = rhobar;
+    st[7] = c_h;
+}
+
+// Device-resident LSQR scalars (gk.hip): the Givens rotation from the sums of squares *ssb
 // (beta^2) and *ssa (alpha^2) in one thread (st = [rho_bar, phi_bar, stop]); the step
 // v /= alpha, x += coef0 w, w = v - coef1 w (skipped after the stop), with ||x - x_true||^2 fused
 // into err_out when xt != NULL; out = in / sqrt(*ss).
@@ -433,26 +494,26 @@ void gkb_mstep(hgm_ctx* c, int64_t n, const T* w, const T* ssa, const T* u, T* t
 // partials re-formed by every block of the division (no k_finalize launch; the same bits)
 template <typename T>
 void gkb_mstep_div(hgm_ctx* c, int64_t n, const T* w, const T* ssa, T* u, T* t, T* av, T* ss_out, bool nz);
-// (one-pass LSQR) A*x and A*w images in double (kernels.hip k_lsqr_img)
+// (one-pass LSQR) A*x and A*w images in double (gk.hip k_lsqr_img)
 template <typename T>
 void lsqr_img(hgm_ctx* c, int64_t m, const T* wm, const T* ssa, const T* coef, const double* st, int k, double* ax,
               double* aw, bool init);
 template <typename T>
 void lsmr_update(hgm_ctx* c, int64_t n, T* x, T* h, T* hbar, const T* v, T c_hbar, T c_x, T c_h,
                  bool first);
-// LSMR kept-product monitor step (kernels.hip: k_lsmr_mon): image of v_k = c1*p1 + c0*p0 (or
+// LSMR kept-product monitor step (gk.hip: k_lsmr_mon): image of v_k = c1*p1 + c0*p0 (or
 // p1 if p0 == nullptr), then the h / hbar / x image recurrences; *out = ||rhs - image(x)||^2
 // (cf != NULL: [c1, c0, f, e, cx] read on the device, from lsmr_rot)
 template <typename T>
 void lsmr_monitor(hgm_ctx* c, int64_t n, const T* p1, const T* p0, double c1, double c0, double* Ih, double* Ihb,
                   double* Ix, const T* rhs, double f, double e, double cx, bool first, double* out,
                   const double* cf = nullptr);
-// The n-space monitor in carried-residual form with T images (the fp32 solves; kernels.hip
+// The n-space monitor in carried-residual form with T images (the fp32 solves; gk.hip
 // k_lsmr_mon_r): Ir starts as A'b; *out = ||Ir_k||^2; coefficients from lsmr_rot's cf.
 template <typename T>
 void lsmr_monitor_r(hgm_ctx* c, int64_t n, const T* p1, const T* p0, T* Ih, T* Ihb, T* Ir, bool first, double* out,
                     const double* cf);
-// Device-resident LSMR scalars (kernels.hip): the rotations :42-67 in one thread from *ssb = beta^2 and
+// Device-resident LSMR scalars (gk.hip): the rotations :42-67 in one thread from *ssb = beta^2 and
 // *ssa = alpha^2 (st = [alpha, alphabar, rho, rhobar, cbar, sbar, zetabar, theta/rho, stop]); the
 // n-space step v /= alpha, hbar / x / h updates (skipped after the stop) with ||x - x_true||^2 fused
 // into err_out when xt != NULL; the stop test :76 on the m-space monitor; out = in / sqrt(*ss)

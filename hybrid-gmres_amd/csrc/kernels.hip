@@ -1,5 +1,6 @@
-// HIP kernels of the Arnoldi/GMRES + Golub-Kahan inner loop other than SpMV (spmv.hip),
-// written for gfx950 (CDNA4).
+// HIP kernels of the Arnoldi/GMRES inner loop other than SpMV (spmv.hip), written for gfx950
+// (CDNA4): the reductions, the MGS sweeps, the Krylov-basis GEMV and the plain elementwise
+// kernels.  The Golub-Kahan solvers' device code (LSQR / LSMR) is gk.hip.
 //
 //  * MGS (hybrid_*_rtp.m:20-26): one launch per Gram-Schmidt pass j fusing
 //    axpy_j (v -= h_j q_j) with the inner product of the NEXT column (q_{j+1}' v).  The
@@ -8,9 +9,7 @@
 //    launch and no host round trip is needed between passes.
 //  * Reductions: per-lane sums -> wave butterfly -> 4-wave LDS sum in fixed order
 //    (single 1024-thread launch for vectors up to 256 Ki entries).
-//  * Krylov-basis GEMV (x = Q y) fused with the error monitor, elementwise GKB updates.
-#include <type_traits>
-
+//  * Krylov-basis GEMV (x = Q y) fused with the error monitor.
 #include "device_common.h"
 
 namespace hgm {
@@ -104,52 +103,6 @@ void fixed_reduce(hgm_ctx* c, int op, int64_t n1, const T* a1, const T* b1, int6
 // ------------------------------------------------------------------------------
 // Reductions
 // ------------------------------------------------------------------------------
-// Grid-stride order of the elementwise kernels with a fused partial sum (VEC: 16-byte vectors of W
-// elements -- thread g of the grid takes vectors g, g + G, ... and their elements in order, and the
-// last block's thread 0 then the n mod W tail; else single elements g, g + G, ...).  Every kernel
-// whose partials must give the same bits as another's (k_lsqr_step's error sum and
-// k_reduce_partial<T, 2>) walks its elements through this.
-template <typename T, bool VEC, typename F>
-__device__ __forceinline__ void grid_elems(int64_t n, F&& f) {
-    if constexpr (VEC) {
-        using V = typename V16<T>::t;
-        constexpr int W = V16<T>::W;
-        (void)sizeof(V);
-        const int64_t nv = n / W;
-#pragma unroll 2
-        for (int64_t g = (int64_t)blockIdx.x * BS + threadIdx.x; g < nv; g += (int64_t)gridDim.x * BS)
-            f(g * W, std::integral_constant<int, W>{});
-        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
-            for (int64_t i = nv * W; i < n; ++i) f(i, std::integral_constant<int, 1>{});
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS)
-            f(i, std::integral_constant<int, 1>{});
-    }
-}
-
-// W consecutive elements from p + i (one 16-byte access for W > 1; i a multiple of W)
-template <int W, typename T>
-__device__ __forceinline__ void vload(const T* p, int64_t i, T (&o)[W]) {
-    if constexpr (W == 1) {
-        o[0] = p[i];
-    } else {
-        const typename V16<T>::t v = *reinterpret_cast<const typename V16<T>::t*>(p + i);
-#pragma unroll
-        for (int e = 0; e < W; ++e) o[e] = v[e];
-    }
-}
-template <int W, typename T>
-__device__ __forceinline__ void vstore(T* p, int64_t i, const T (&o)[W]) {
-    if constexpr (W == 1) {
-        p[i] = o[0];
-    } else {
-        typename V16<T>::t v;
-#pragma unroll
-        for (int e = 0; e < W; ++e) v[e] = o[e];
-        *reinterpret_cast<typename V16<T>::t*>(p + i) = v;
-    }
-}
-
 template <typename T, int OP, bool VEC>   // 0: a.b   1: a.a   2: (a-b).(a-b)
 __global__ __launch_bounds__(BS) void k_reduce_partial(int64_t n, const T* __restrict__ a,
                                                        const T* __restrict__ b,
@@ -178,6 +131,13 @@ __global__ __launch_bounds__(BS) void k_finalize(const T* __restrict__ parts, in
     const T r = reduce_parts(parts + (int64_t)blockIdx.x * np, np, sh);
     if (threadIdx.x == 0) st_sys(out + blockIdx.x, r);
 }
+
+template <typename T>
+void finalize_parts(hgm_ctx* c, const T* parts, int np, T* out) {
+    k_finalize<T><<<1, BS, 0, c->stream>>>(parts, np, out);
+}
+template void finalize_parts<double>(hgm_ctx*, const double*, int, double*);
+template void finalize_parts<float>(hgm_ctx*, const float*, int, float*);
 
 // Single-launch reduction for short vectors (one 1024-thread block, fixed order).
 template <typename T, int OP>
@@ -211,8 +171,6 @@ __global__ __launch_bounds__(1024) void k_reduce_single(int64_t n, const T* __re
         st_sys(out, r);
     }
 }
-
-constexpr int64_t SINGLE_MAX = 1 << 15;   // vectors up to 32 Ki entries: one launch
 
 template <typename T, int OP>
 static void reduce_to(hgm_ctx* c, int64_t n, const T* a, const T* b, T* out) {
@@ -1461,699 +1419,11 @@ template <typename T> void normalize_to(hgm_ctx* c, int64_t n, T* v, T* nrm_out)
         HGM_HIP(hipGetLastError());
         return;
     }
-    const int np = parts_for(n);
-    T* parts = c->buf<T>("red_parts", MAX_PARTS);
-    if (al16(v)) k_reduce_partial<T, 1, true><<<np, BS, 0, c->stream>>>(n, v, v, parts);
-    else k_reduce_partial<T, 1, false><<<np, BS, 0, c->stream>>>(n, v, v, parts);
-    k_vnorm<T><<<grid_for(n), BS, 0, c->stream>>>(n, v, parts, np, nrm_out);
-    HGM_HIP(hipGetLastError());
-}
-
-// lsqr_solver.m:40-41:  x = x + (phi/rho) w ;  w = v - (theta/rho) w
-template <typename T>
-__global__ __launch_bounds__(BS) void k_lsqr_update(int64_t n, T* __restrict__ x, T* __restrict__ w,
-                                                    const T* __restrict__ v, T a, T b) {
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const T wi = w[i];
-        const T p = a * wi;
-        x[i] = x[i] + p;
-        const T q = b * wi;
-        w[i] = v[i] - q;
-    }
-}
-template <typename T> void lsqr_update(hgm_ctx* c, int64_t n, T* x, T* w, const T* v, T a, T b) {
-    k_lsqr_update<T><<<grid_for(n), BS, 0, c->stream>>>(n, x, w, v, a, b);
-    HGM_HIP(hipGetLastError());
-}
-
-// ------------------------------------------------------------------------------
-// Device-resident LSQR scalars (lsqr_solver.m:22-46 without host round trips): the Givens
-// rotation of :31-38 in one thread, in double, exactly as the host loop computes it from the
-// same sums of squares, and the stop test of :44-46 as a flag the update kernel honours.
-// st: [rho_bar, phi_bar, stop] (stop = iteration+1 of the first res <= tol, 0 while running).
-// ------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void scalar_copies(const ScalarCopy<T>& cp) {
-    if (cp.dst) *cp.dst = *cp.src;
-    if (cp.ddst) *cp.ddst = *cp.dsrc;
-}
-template <typename T>
-__global__ void k_copy_scalars(ScalarCopy<T> cp) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) scalar_copies(cp);
-}
-template <typename T>
-void copy_scalars(hgm_ctx* c, const ScalarCopy<T>& cp) {
-    k_copy_scalars<T><<<1, 64, 0, c->stream>>>(cp);
-    HGM_HIP(hipGetLastError());
-}
-template void copy_scalars<double>(hgm_ctx*, const ScalarCopy<double>&);
-template void copy_scalars<float>(hgm_ctx*, const ScalarCopy<float>&);
-
-template <typename T>
-__global__ void k_lsqr_rot(const T* ssb, const T* ssa, double* st, T* coef, double* phib_hist, int k, double nb,
-                           double tol, ScalarCopy<T> cp) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    scalar_copies(cp);
-    const double beta = sqrt((double)*ssb);                  // :23
-    const double alpha = sqrt((double)*ssa);                 // :27
-    const double rho_bar = st[0], phi_bar = st[1];
-    const double rho = sqrt(rho_bar * rho_bar + beta * beta);   // :31
-    const double cs = rho_bar / rho;                         // :32
-    const double sn = beta / rho;                            // :33
-    const double theta = sn * alpha;                         // :34
-    st[0] = -cs * alpha;                                     // :35
-    const double phi = cs * phi_bar;                         // :37
-    const double pb = sn * phi_bar;                          // :38
-    st[1] = pb;
-    coef[0] = (T)(phi / rho);                                // :40
-    coef[1] = (T)(theta / rho);                              // :41
-    phib_hist[k] = pb;
-    if (st[2] == 0.0 && fabs(pb) / nb <= tol) st[2] = (double)(k + 1);   // :44-46
-}
-
-// v = v_hat / alpha (alpha = sqrt(*ssa)), then x += (phi/rho) w ; w = v - (theta/rho) w
-// (lsqr_solver.m:28,40-41), skipped once an earlier iteration met the stop test; with parts,
-// also the partials of ||x - x_true||^2 (:43) in k_reduce_partial<T, 2>'s order (same bits).
-template <typename T, bool VEC>
-__global__ __launch_bounds__(BS) void k_lsqr_step(int64_t n, T* __restrict__ x, T* __restrict__ w, T* __restrict__ v,
-                                                  const T* ssa, const T* coef, const double* st, int k,
-                                                  const T* __restrict__ xt, T* __restrict__ parts) {
-    __shared__ T sh[4];
-    const T alpha = (T)sqrt((double)*ssa);
-    const bool live = !(st[2] != 0.0 && st[2] < (double)(k + 1));
-    const T a = coef[0], b = coef[1];
-    T acc = 0;
-    grid_elems<T, VEC>(n, [&](int64_t i, auto wc) {
-        constexpr int W = decltype(wc)::value;
-        T vv[W], xx[W], ww[W], tt[W];
-        vload<W>(v, i, vv);
-        vload<W>(x, i, xx);
-        if (live) vload<W>(w, i, ww);
-        if (parts) vload<W>(xt, i, tt);
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            vv[e] = vv[e] / alpha;
-            if (live) {
-                const T p = a * ww[e];
-                xx[e] = xx[e] + p;
-                const T q = b * ww[e];
-                ww[e] = vv[e] - q;
-            }
-            if (parts) {
-                const T d = xx[e] - tt[e];
-                acc += d * d;
-            }
-        }
-        vstore<W>(v, i, vv);
-        if (live) {
-            vstore<W>(x, i, xx);
-            vstore<W>(w, i, ww);
-        }
-    });
-    if (parts) {
-        const T tot = block_sum_all(acc, sh);
-        if (threadIdx.x == 0) parts[blockIdx.x] = tot;
-    }
-}
-
-// out = in / (T)sqrt((double)*ss)
-template <typename T>
-__global__ __launch_bounds__(BS) void k_div_sqrt(int64_t n, const T* __restrict__ in, T* __restrict__ out, const T* ss) {
-    const T s = (T)sqrt((double)*ss);
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) out[i] = in[i] / s;
-}
-
-template <typename T>
-void lsqr_rot(hgm_ctx* c, const T* ssb, const T* ssa, double* st, T* coef, double* phib_hist, int k, double nb,
-              double tol, const ScalarCopy<T>& cp) {
-    k_lsqr_rot<T><<<1, 64, 0, c->stream>>>(ssb, ssa, st, coef, phib_hist, k, nb, tol, cp);
-    HGM_HIP(hipGetLastError());
-}
-
-template <typename T>
-void lsqr_step(hgm_ctx* c, int64_t n, T* x, T* w, T* v, const T* ssa, const T* coef, const double* st, int k,
-               const T* xt, T* err_out) {
-    // the error partials keep reduce_to's layout: one launch for short vectors stays separate
-    const bool fuse = xt && n > SINGLE_MAX && !c->num.parity;
-    const int np = fuse ? parts_for(n) : grid_for(n);
-    T* parts = fuse ? c->buf<T>("red_parts", MAX_PARTS) : nullptr;
-    // (vectors as k_reduce_partial takes them for the same x and x_true: the same error bits)
-    if (al16(x) && al16(w) && al16(v) && (!xt || al16(xt)))
-        k_lsqr_step<T, true><<<np, BS, 0, c->stream>>>(n, x, w, v, ssa, coef, st, k, xt, parts);
-    else
-        k_lsqr_step<T, false><<<np, BS, 0, c->stream>>>(n, x, w, v, ssa, coef, st, k, xt, parts);
-    if (fuse) k_finalize<T><<<1, BS, 0, c->stream>>>(parts, np, err_out);
-    HGM_HIP(hipGetLastError());
-    if (xt && !fuse) sumsq_diff<T>(c, n, x, xt, err_out);
-}
-
-template <typename T>
-void div_sqrt(hgm_ctx* c, int64_t n, const T* in, T* out, const T* ss) {
-    k_div_sqrt<T><<<grid_for(n), BS, 0, c->stream>>>(n, in, out, ss);
-    HGM_HIP(hipGetLastError());
-}
-
-// The m-space half of a Golub-Kahan step after the one-pass w = A*(A'*u - beta*v) (fused.hip):
-// A*v_k = w / alpha_k (alpha = (T)sqrt((double)*ssa); a zero alpha leaves w, as lsmr_solver.m:16/40
-// leave v undivided), kept in av when given, then t = A*v_k - alpha*u (lsqr_solver.m:22,
-// lsmr_solver.m:34; two roundings, as the two-pass EPI_SUB epilogue), with the partials of ||t||^2
-// in k_reduce_partial<T, 1>'s layout (parts == nullptr: none).
-template <typename T, bool VEC>
-__global__ __launch_bounds__(BS) void k_gkb_mstep(int64_t n, const T* __restrict__ w, const T* ssa,
-                                                  const T* __restrict__ u, T* __restrict__ t, T* __restrict__ av,
-                                                  T* __restrict__ parts) {
-    __shared__ T sh[4];
-    const T a = (T)sqrt((double)*ssa);
-    T acc = 0;
-    grid_elems<T, VEC>(n, [&](int64_t i, auto wc) {
-        constexpr int W = decltype(wc)::value;
-        T ww[W], uu[W], tt[W];
-        vload<W>(w, i, ww);
-        vload<W>(u, i, uu);
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            ww[e] = a != T(0) ? ww[e] / a : ww[e];
-            const T s = a * uu[e];
-            tt[e] = ww[e] - s;
-            acc += tt[e] * tt[e];
-        }
-        if (av) vstore<W>(av, i, ww);
-        vstore<W>(t, i, tt);
-    });
-    if (parts) {
-        const T tot = block_sum_all(acc, sh);
-        if (threadIdx.x == 0) parts[blockIdx.x] = tot;
-    }
-}
-
-template <typename T>
-void gkb_mstep(hgm_ctx* c, int64_t n, const T* w, const T* ssa, const T* u, T* t, T* av, T* ss_out) {
-    const bool fuse = n > SINGLE_MAX && !c->num.parity;
-    const int np = fuse ? parts_for(n) : grid_for(n);
-    T* parts = fuse ? c->buf<T>("red_parts", MAX_PARTS) : nullptr;
-    if (al16(w) && al16(u) && al16(t) && (!av || al16(av)))
-        k_gkb_mstep<T, true><<<np, BS, 0, c->stream>>>(n, w, ssa, u, t, av, parts);
-    else
-        k_gkb_mstep<T, false><<<np, BS, 0, c->stream>>>(n, w, ssa, u, t, av, parts);
-    if (fuse) k_finalize<T><<<1, BS, 0, c->stream>>>(parts, np, ss_out);
-    HGM_HIP(hipGetLastError());
-    if (!fuse) sumsq<T>(c, n, t, ss_out);
-}
-template void gkb_mstep<double>(hgm_ctx*, int64_t, const double*, const double*, const double*, double*, double*,
-                                double*);
-
-// out = in / s with s = (T)sqrt(ss), ss the sum of the np partials of ||in||^2 that every block
-// re-forms in k_finalize's order (reduce_parts: the same bits); block 0 publishes ss to ss_out.
-// NZ: a zero s leaves in (lsmr_solver.m:36, as k_div_sqrt_nz).  Round 6: replaces the
-// k_finalize + k_div_sqrt launch pair of the one-pass Golub-Kahan m-space step.
-template <typename T, bool NZ>
-__global__ __launch_bounds__(BS) void k_div_sqrt_parts(int64_t n, const T* __restrict__ in, T* __restrict__ out,
-                                                       const T* __restrict__ parts, int np, T* ss_out) {
-    __shared__ T sh[4];
-    const T ssv = reduce_parts(parts, np, sh);
-    if (blockIdx.x == 0 && threadIdx.x == 0) st_sys(ss_out, ssv);
-    const T s = (T)sqrt((double)ssv);
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS)
-        out[i] = (!NZ || s > T(0)) ? in[i] / s : in[i];
-}
-
-// gkb_mstep (t = A*v_k - alpha*u, ||t||^2 -> ss_out) followed by u = t / sqrt(||t||^2) (NZ: as
-// div_sqrt_nz): two launches where the separate calls take three (the same bits).
-template <typename T>
-void gkb_mstep_div(hgm_ctx* c, int64_t n, const T* w, const T* ssa, T* u, T* t, T* av, T* ss_out, bool nz) {
-    const bool fuse = n > SINGLE_MAX && !c->num.parity;
-    if (!fuse) {
-        gkb_mstep<T>(c, n, w, ssa, u, t, av, ss_out);
-        if (nz) div_sqrt_nz<T>(c, n, t, u, ss_out);
-        else div_sqrt<T>(c, n, t, u, ss_out);
-        return;
-    }
-    const int np = parts_for(n);
-    T* parts = c->buf<T>("red_parts", MAX_PARTS);
-    if (al16(w) && al16(u) && al16(t) && (!av || al16(av)))
-        k_gkb_mstep<T, true><<<np, BS, 0, c->stream>>>(n, w, ssa, u, t, av, parts);
-    else
-        k_gkb_mstep<T, false><<<np, BS, 0, c->stream>>>(n, w, ssa, u, t, av, parts);
-    if (nz) k_div_sqrt_parts<T, true><<<grid_for(n), BS, 0, c->stream>>>(n, t, u, parts, np, ss_out);
-    else k_div_sqrt_parts<T, false><<<grid_for(n), BS, 0, c->stream>>>(n, t, u, parts, np, ss_out);
-    HGM_HIP(hipGetLastError());
-}
-template void gkb_mstep_div<double>(hgm_ctx*, int64_t, const double*, const double*, double*, double*, double*,
-                                    double*, bool);
-template void gkb_mstep_div<float>(hgm_ctx*, int64_t, const float*, const float*, float*, float*, float*, float*,
-                                   bool);
-template void gkb_mstep<float>(hgm_ctx*, int64_t, const float*, const float*, const float*, float*, float*, float*);
-
-// (one-pass LSQR) the images of x and w under A, in double, so the exact final residual of
-// lsqr_solver.m:52 needs no SpMV: with A*v_{k+1} = w_m / alpha_{k+1} (the pass's A*v_hat),
-// A*x += (phi/rho) A*w ; A*w = A*v_{k+1} - (theta/rho) A*w (:40-41 under A).  init: A*w = A*v_0,
-// A*x = 0.  Iterations enqueued past a device stop (st[2], as k_lsqr_step) change nothing.
-template <typename T>
-__global__ __launch_bounds__(BS) void k_lsqr_img(int64_t m, const T* __restrict__ wm, const T* ssa, const T* coef,
-                                                 const double* st, int k, double* __restrict__ ax,
-                                                 double* __restrict__ aw, int init) {
-    const double a = (double)(T)sqrt((double)*ssa);
-    const bool live = init || !(st[2] != 0.0 && st[2] < (double)(k + 1));
-    if (!live) return;
-    const double c0 = init ? 0.0 : (double)coef[0], c1 = init ? 0.0 : (double)coef[1];
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < m; i += (int64_t)gridDim.x * BS) {
-        const double av = a != 0.0 ? (double)wm[i] / a : (double)wm[i];
-        if (init) {
-            ax[i] = 0.0;
-            aw[i] = av;
-        } else {
-            ax[i] = ax[i] + c0 * aw[i];
-            aw[i] = av - c1 * aw[i];
-        }
-    }
-}
-template <typename T>
-void lsqr_img(hgm_ctx* c, int64_t m, const T* wm, const T* ssa, const T* coef, const double* st, int k, double* ax,
-              double* aw, bool init) {
-    k_lsqr_img<T><<<grid_for(m), BS, 0, c->stream>>>(m, wm, ssa, coef, st, k, ax, aw, init ? 1 : 0);
-    HGM_HIP(hipGetLastError());
-}
-template void lsqr_img<double>(hgm_ctx*, int64_t, const double*, const double*, const double*, const double*, int,
-                               double*, double*, bool);
-template void lsqr_img<float>(hgm_ctx*, int64_t, const float*, const float*, const float*, const double*, int,
-                              double*, double*, bool);
-
-// lsmr_solver.m:61-67
-template <typename T, bool FIRST>
-__global__ __launch_bounds__(BS) void k_lsmr_update(int64_t n, T* __restrict__ x, T* __restrict__ h,
-                                                    T* __restrict__ hbar, const T* __restrict__ v,
-                                                    T c_hbar, T c_x, T c_h) {
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        const T hi = h[i];
-        T hb;
-        if (FIRST) hb = hi;                              // :62  hbar = h
-        else { const T p = c_hbar * hbar[i]; hb = hi - p; }   // :64
-        hbar[i] = hb;
-        const T q = c_x * hb;
-        x[i] = x[i] + q;                                 // :66
-        const T r = c_h * hi;
-        h[i] = v[i] - r;                                 // :67
-    }
-}
-template <typename T>
-void lsmr_update(hgm_ctx* c, int64_t n, T* x, T* h, T* hbar, const T* v, T c_hbar, T c_x, T c_h, bool first) {
-    if (first) k_lsmr_update<T, true><<<grid_for(n), BS, 0, c->stream>>>(n, x, h, hbar, v, c_hbar, c_x, c_h);
-    else k_lsmr_update<T, false><<<grid_for(n), BS, 0, c->stream>>>(n, x, h, hbar, v, c_hbar, c_x, c_h);
-    HGM_HIP(hipGetLastError());
-}
-
-// Device-resident LSMR scalars (lsmr_solver.m:42-67), the host loop's double arithmetic in one
-// thread.  st = [alpha, alphabar, rho, rhobar, cbar, sbar, zetabar, prev (theta/rho), stop];
-// *ssb = beta^2, *ssa = alpha^2 of this step.  coef = (T)[c_hbar, c_x, c_h] of :64/:66/:67 for the
-// n-space update; cfm / cfn = the monitors' coefficients [c1, c0, f, e, cx] (m-space: image of
-// v = A*v_k; n-space: beta A'u_{k+1} + alpha_k A'u_k).
-template <typename T>
-__global__ void k_lsmr_rot(const T* ssb, const T* ssa, double* st, T* coef, double* cfm, double* cfn,
-                           ScalarCopy<T> cp) {
-    if (threadIdx.x != 0) return;
-    scalar_copies(cp);
-    const double alpha_k = st[0];
-    const double beta = sqrt((double)*ssb), alpha = sqrt((double)*ssa);   // :35, :39
-    const double alphahat = st[1];                                        // :42
-    const double rhoold = st[2];                                          // :43
-    const double rho = hypot(alphahat, beta);                             // :44
-    const double cc = alphahat / rho, ss = beta / rho;                    // :45-46
-    const double thetanew = ss * alpha;                                   // :48
-    st[1] = cc * alpha;                                                   // :49 alphabar
-    const double rhobarold = st[3];                                       // :51
-    const double thetabar = st[5] * rho;                                  // :52
-    const double cr = st[4] * rho;
-    const double rhobar = hypot(cr, thetanew);                            // :53
-    st[4] = cr / rhobar;                                                  // :54 cbar
-    st[5] = thetanew / rhobar;                                            // :55 sbar
-    const double zeta = st[4] * st[6];                                    // :58
-    st[6] = -st[5] * st[6];                                               // :59 zetabar
-    const double c_hbar = (thetabar * rho) / (rhoold * rhobarold);        // :64
-    const double c_x = zeta / (rho * rhobar);                             // :66
-    const double c_h = thetanew / rho;                                    // :67
-    coef[0] = (T)c_hbar;
-    coef[1] = (T)c_x;
-    coef[2] = (T)c_h;
-    const double f = st[7];
-    const double m5[5] = {1.0, 0.0, f, c_hbar, c_x}, n5[5] = {beta, alpha_k, f, c_hbar, c_x};
-    for (int i = 0; i < 5; ++i) {
-        cfm[i] = m5[i];
-        cfn[i] = n5[i];
-    }
-    st[0] = alpha;
-    st[2] = rho;
-    st[3] = rhobar;
-    st[7] = c_h;
-}
-
-// The n-space LSMR step (lsmr_solver.m:40, :61-67) with device coefficients: v = v / alpha
-// (alpha = (T)sqrt(*ssa); a zero alpha leaves v, :40), hbar = h - c_hbar hbar (k = 0: h), x += c_x hbar,
-// h = v - c_h h -- x, h, hbar untouched once an earlier iteration met the stop test -- and, with
-// parts, the partials of ||x - x_true||^2 (:72) in k_lsqr_step's layout.
-template <typename T, bool FIRST, bool VEC>
-__global__ __launch_bounds__(BS) void k_lsmr_step(int64_t n, T* __restrict__ x, T* __restrict__ h,
-                                                  T* __restrict__ hbar, T* __restrict__ v, const T* ssa,
-                                                  const T* coef, const double* st, int k, const T* __restrict__ xt,
-                                                  T* __restrict__ parts) {
-    __shared__ T sh[4];
-    const T alpha = (T)sqrt((double)*ssa);
-    const bool live = !(st[8] != 0.0 && st[8] < (double)(k + 1));
-    const T c_hbar = coef[0], c_x = coef[1], c_h = coef[2];
-    T acc = 0;
-    grid_elems<T, VEC>(n, [&](int64_t i, auto wc) {
-        constexpr int W = decltype(wc)::value;
-        T vv[W], xx[W], hh[W], hb[W], tt[W];
-        vload<W>(v, i, vv);
-        vload<W>(x, i, xx);
-        if (live) {
-            vload<W>(h, i, hh);
-            if (!FIRST) vload<W>(hbar, i, hb);
-        }
-        if (parts) vload<W>(xt, i, tt);
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            if (alpha > T(0)) vv[e] = vv[e] / alpha;                 // :40
-            if (live) {
-                if (FIRST) hb[e] = hh[e];                            // :62
-                else { const T p = c_hbar * hb[e]; hb[e] = hh[e] - p; }   // :64
-                const T q = c_x * hb[e];
-                xx[e] = xx[e] + q;                                   // :66
-                const T r = c_h * hh[e];
-                hh[e] = vv[e] - r;                                   // :67
-            }
-            if (parts) {
-                const T d = xx[e] - tt[e];
-                acc += d * d;
-            }
-        }
-        if (alpha > T(0)) vstore<W>(v, i, vv);
-        if (live) {
-            vstore<W>(hbar, i, hb);
-            vstore<W>(x, i, xx);
-            vstore<W>(h, i, hh);
-        }
-    });
-    if (parts) {
-        const T tot = block_sum_all(acc, sh);
-        if (threadIdx.x == 0) parts[blockIdx.x] = tot;
-    }
-}
-
-// :76 on the device: st[8] = k + 1 at the first iteration with sqrt(||r||^2) / (||b|| + eps) < tol
-__global__ void k_lsmr_stop(const double* rr, double nb, double tol, double* st, int k) {
-    if (threadIdx.x != 0) return;
-    const double res = sqrt(rr[0]) / (nb + 0x1p-52);   // eps
-    if (st[8] == 0.0 && res < tol) st[8] = (double)(k + 1);
-}
-
-// out = in / sqrt(*ss), or in when the sum is zero (lsmr_solver.m:36: if beta > 0, u = u / beta)
-template <typename T>
-__global__ __launch_bounds__(BS) void k_div_sqrt_nz(int64_t n, const T* __restrict__ in, T* __restrict__ out,
-                                                    const T* ss) {
-    const T s = (T)sqrt((double)*ss);
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS)
-        out[i] = s > T(0) ? in[i] / s : in[i];
-}
-
-template <typename T>
-void lsmr_rot(hgm_ctx* c, const T* ssb, const T* ssa, double* st, T* coef, double* cfm, double* cfn,
-              const ScalarCopy<T>& cp) {
-    k_lsmr_rot<T><<<1, 64, 0, c->stream>>>(ssb, ssa, st, coef, cfm, cfn, cp);
-    HGM_HIP(hipGetLastError());
-}
-
-template <typename T>
-void lsmr_step(hgm_ctx* c, int64_t n, T* x, T* h, T* hbar, T* v, const T* ssa, const T* coef, const double* st,
-               int k, const T* xt, T* err_out) {
-    const bool fuse = xt && n > SINGLE_MAX;
-    const int np = fuse ? parts_for(n) : grid_for(n);
-    T* parts = fuse ? c->buf<T>("red_parts", MAX_PARTS) : nullptr;
-    const bool vec = al16(x) && al16(h) && al16(hbar) && al16(v) && (!xt || al16(xt));
-    if (k == 0 && vec) k_lsmr_step<T, true, true><<<np, BS, 0, c->stream>>>(n, x, h, hbar, v, ssa, coef, st, k, xt, parts);
-    else if (k == 0) k_lsmr_step<T, true, false><<<np, BS, 0, c->stream>>>(n, x, h, hbar, v, ssa, coef, st, k, xt, parts);
-    else if (vec) k_lsmr_step<T, false, true><<<np, BS, 0, c->stream>>>(n, x, h, hbar, v, ssa, coef, st, k, xt, parts);
-    else k_lsmr_step<T, false, false><<<np, BS, 0, c->stream>>>(n, x, h, hbar, v, ssa, coef, st, k, xt, parts);
-    if (fuse) k_finalize<T><<<1, BS, 0, c->stream>>>(parts, np, err_out);
-    HGM_HIP(hipGetLastError());
-    if (xt && !fuse) sumsq_diff<T>(c, n, x, xt, err_out);
-}
-
-void lsmr_stop(hgm_ctx* c, const double* rr, double nb, double tol, double* st, int k) {
-    k_lsmr_stop<<<1, 64, 0, c->stream>>>(rr, nb, tol, st, k);
-    HGM_HIP(hipGetLastError());
-}
-
-template <typename T>
-void div_sqrt_nz(hgm_ctx* c, int64_t n, const T* in, T* out, const T* ss) {
-    k_div_sqrt_nz<T><<<grid_for(n), BS, 0, c->stream>>>(n, in, out, ss);
-    HGM_HIP(hipGetLastError());
-}
-
-// LSMR monitors from kept products.  The images of the LSMR vectors under A
-// and A'A follow the same recurrences as the vectors (lsmr_solver.m:61-67), fed by the raw
-// products the bidiagonalisation already forms:
-//   m-space: A*h_k = A*v_k - f*A*h_{k-1};  A*hbar_k = A*h_k - e*A*hbar_{k-1};  A*x_k = A*x_{k-1} + cx*A*hbar_k
-//   n-space: A'A*v_k = beta_{k+1} A'u_{k+1} + alpha_k A'u_k  (A*v_k = beta_{k+1} u_{k+1} + alpha_k u_k,
-//            lsmr_solver.m:34-36), then the same three updates for A'A*h, A'A*hbar, A'A*x.
-// r = b - A*x (:69) and A'r = A'b - A'A*x (:71) are then norms of kept vectors.  The images are
-// accumulated in fp64 for both value types.  parts[blk] = this block's sum of the squared
-// monitor vector.
-// cf != NULL: the coefficients [c1, c0, f, e, cx] from the device (k_lsmr_rot) instead of the arguments.
-template <typename T, bool FIRST>
-__global__ __launch_bounds__(BS) void k_lsmr_mon(int64_t n, const T* __restrict__ p1, const T* __restrict__ p0,
-                                                 double c1, double c0, double* __restrict__ Ih,
-                                                 double* __restrict__ Ihb, double* __restrict__ Ix,
-                                                 const T* __restrict__ rhs, double f, double e, double cx,
-                                                 double* __restrict__ parts, const double* __restrict__ cf) {
-    __shared__ double sh[4];
-    if (cf) {
-        c1 = cf[0];
-        c0 = cf[1];
-        f = cf[2];
-        e = cf[3];
-        cx = cf[4];
-    }
-    double acc = 0;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += (int64_t)gridDim.x * BS) {
-        double iv;                                          // image of v_k
-        if (p0) { const double a = c1 * (double)p1[i], b = c0 * (double)p0[i]; iv = a + b; }
-        else iv = (double)p1[i];
-        double ih, ihb;
-        if (FIRST) { ih = iv; ihb = ih; }                  // h_0 = v_0 (:25), hbar_0 = h_0 (:62)
-        else {
-            const double q = f * Ih[i];
-            ih = iv - q;
-            const double w = e * Ihb[i];
-            ihb = ih - w;
-        }
-        const double s = cx * ihb;
-        const double ix = Ix[i] + s;
-        Ih[i] = ih;
-        Ihb[i] = ihb;
-        Ix[i] = ix;
-        const double d = (double)rhs[i] - ix;
-        acc += d * d;
-    }
-    const double tot = block_sum_all(acc, sh);
-    if (threadIdx.x == 0) parts[blockIdx.x] = tot;
-}
-
-// The n-space monitor of the fp32 solves in carried-residual form: the images of h and hbar and
-// the normal-equations residual Ir = A'b - A'A*x itself (Ir_0 = A'b) are stored in T and updated in
-// double, Ir_k = Ir_{k-1} - cx * image(hbar_k); parts = sum Ir_k^2 (the rounded values carried on).
-// Carrying Ir instead of image(x) keeps the small residual from a cancellation against A'b, so T
-// storage holds its relative accuracy; it moves 3 T arrays twice plus p1, p0 per iteration instead
-// of 3 double arrays twice plus p1, p0 and A'b (C5: 0.54 against 1.0 GB).
-template <typename T, bool FIRST, bool VEC>
-__global__ __launch_bounds__(BS) void k_lsmr_mon_r(int64_t n, const T* __restrict__ p1, const T* __restrict__ p0,
-                                                   T* __restrict__ Ih, T* __restrict__ Ihb, T* __restrict__ Ir,
-                                                   double* __restrict__ parts, const double* __restrict__ cf) {
-    __shared__ double sh[4];
-    const double c1 = cf[0], c0 = cf[1], f = cf[2], e = cf[3], cx = cf[4];
-    double acc = 0;
-    grid_elems<T, VEC>(n, [&](int64_t i, auto wc) {
-        constexpr int W = decltype(wc)::value;
-        T a[W], b[W], h[W], hb[W], r[W];
-        vload<W>(p1, i, a);
-        vload<W>(p0, i, b);
-        if (!FIRST) {
-            vload<W>(Ih, i, h);
-            vload<W>(Ihb, i, hb);
-        }
-        vload<W>(Ir, i, r);
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            const double x1 = c1 * (double)a[u], x0 = c0 * (double)b[u];
-            const double iv = x1 + x0;
-            double ih, ihb;
-            if (FIRST) { ih = iv; ihb = ih; }
-            else {
-                const double q = f * (double)h[u];
-                ih = iv - q;
-                const double w = e * (double)hb[u];
-                ihb = ih - w;
-            }
-            const double s = cx * ihb;
-            const double ir = (double)r[u] - s;
-            h[u] = (T)ih;
-            hb[u] = (T)ihb;
-            r[u] = (T)ir;
-            const double rr = (double)r[u];
-            acc += rr * rr;
-        }
-        vstore<W>(Ih, i, h);
-        vstore<W>(Ihb, i, hb);
-        vstore<W>(Ir, i, r);
-    });
-    const double tot = block_sum_all(acc, sh);
-    if (threadIdx.x == 0) parts[blockIdx.x] = tot;
-}
-
-template <typename T>
-void lsmr_monitor_r(hgm_ctx* c, int64_t n, const T* p1, const T* p0, T* Ih, T* Ihb, T* Ir, bool first, double* out,
-                    const double* cf) {
-    const int np = parts_for(n);
-    double* parts = c->buf<double>("lsmr_mon_parts", MAX_PARTS);
-    const bool vec = al16(p1) && al16(p0) && al16(Ih) && al16(Ihb) && al16(Ir);
-#define HGM_MONR(F, V) k_lsmr_mon_r<T, F, V><<<np, BS, 0, c->stream>>>(n, p1, p0, Ih, Ihb, Ir, parts, cf)
-    if (first && vec) HGM_MONR(true, true);
-    else if (first) HGM_MONR(true, false);
-    else if (vec) HGM_MONR(false, true);
-    else HGM_MONR(false, false);
-#undef HGM_MONR
-    k_finalize<double><<<1, BS, 0, c->stream>>>(parts, np, out);
-    HGM_HIP(hipGetLastError());
-}
-
-// k_lsmr_step and k_lsmr_mon_r in one pass over the n-space (the fp32 one-pass LSMR with x_true):
-// the two kernels walk the same elements in the same grid (parts_for(n) blocks, grid_elems) and
-// touch disjoint vectors, so each of the two block sums -- and every element -- has the bits of
-// the two separate launches; one launch boundary and one sweep of the grid instead of two.
-template <typename T, bool FIRST>
-__global__ __launch_bounds__(BS) void k_lsmr_step_mon(int64_t n, T* __restrict__ x, T* __restrict__ h,
-                                                      T* __restrict__ hbar, T* __restrict__ v, const T* ssa,
-                                                      const T* coef, const double* st, int k, const T* __restrict__ xt,
-                                                      T* __restrict__ parts_e, const T* __restrict__ p1,
-                                                      const T* __restrict__ p0, T* __restrict__ Ih, T* __restrict__ Ihb,
-                                                      T* __restrict__ Ir, double* __restrict__ parts_m,
-                                                      const double* __restrict__ cf) {
-    __shared__ T sh[4];
-    __shared__ double shm[4];
-    const T alpha = (T)sqrt((double)*ssa);
-    const bool live = !(st[8] != 0.0 && st[8] < (double)(k + 1));
-    const T c_hbar = coef[0], c_x = coef[1], c_h = coef[2];
-    const double c1 = cf[0], c0 = cf[1], f = cf[2], e = cf[3], cx = cf[4];
-    T acc = 0;
-    double accm = 0;
-    grid_elems<T, true>(n, [&](int64_t i, auto wc) {
-        constexpr int W = decltype(wc)::value;
-        {   // k_lsmr_step's element body
-            T vv[W], xx[W], hh[W], hb[W], tt[W];
-            vload<W>(v, i, vv);
-            vload<W>(x, i, xx);
-            if (live) {
-                vload<W>(h, i, hh);
-                if (!FIRST) vload<W>(hbar, i, hb);
-            }
-            vload<W>(xt, i, tt);
-#pragma unroll
-            for (int u = 0; u < W; ++u) {
-                if (alpha > T(0)) vv[u] = vv[u] / alpha;
-                if (live) {
-                    if (FIRST) hb[u] = hh[u];
-                    else { const T p = c_hbar * hb[u]; hb[u] = hh[u] - p; }
-                    const T q = c_x * hb[u];
-                    xx[u] = xx[u] + q;
-                    const T r = c_h * hh[u];
-                    hh[u] = vv[u] - r;
-                }
-                const T d = xx[u] - tt[u];
-                acc += d * d;
-            }
-            if (alpha > T(0)) vstore<W>(v, i, vv);
-            if (live) {
-                vstore<W>(hbar, i, hb);
-                vstore<W>(x, i, xx);
-                vstore<W>(h, i, hh);
-            }
-        }
-        {   // k_lsmr_mon_r's element body
-            T a[W], b[W], hm[W], hbm[W], r[W];
-            vload<W>(p1, i, a);
-            vload<W>(p0, i, b);
-            if (!FIRST) {
-                vload<W>(Ih, i, hm);
-                vload<W>(Ihb, i, hbm);
-            }
-            vload<W>(Ir, i, r);
-#pragma unroll
-            for (int u = 0; u < W; ++u) {
-                const double x1 = c1 * (double)a[u], x0 = c0 * (double)b[u];
-                const double iv = x1 + x0;
-                double ih, ihb;
-                if (FIRST) { ih = iv; ihb = ih; }
-                else {
-                    const double q = f * (double)hm[u];
-                    ih = iv - q;
-                    const double w = e * (double)hbm[u];
-                    ihb = ih - w;
-                }
-                const double s_ = cx * ihb;
-                const double ir = (double)r[u] - s_;
-                hm[u] = (T)ih;
-                hbm[u] = (T)ihb;
-                r[u] = (T)ir;
-                const double rr = (double)r[u];
-                accm += rr * rr;
-            }
-            vstore<W>(Ih, i, hm);
-            vstore<W>(Ihb, i, hbm);
-            vstore<W>(Ir, i, r);
-        }
-    });
-    const T tot = block_sum_all(acc, sh);
-    const double totm = block_sum_all(accm, shm);
-    if (threadIdx.x == 0) {
-        parts_e[blockIdx.x] = tot;
-        parts_m[blockIdx.x] = totm;
-    }
-}
-
-// The fused pair when it gives the separate launches' bits (x_true given, the partial-sum grid,
-// 16-byte aligned vectors); false: the caller runs lsmr_step and lsmr_monitor_r.
-template <typename T>
-bool lsmr_step_mon(hgm_ctx* c, int64_t n, T* x, T* h, T* hbar, T* v, const T* ssa, const T* coef, const double* st,
-                   int k, const T* xt, T* err_out, const T* p1, const T* p0, T* Ih, T* Ihb, T* Ir, bool first,
-                   double* mon_out, const double* cf) {
-    if (!c->num.lsmr_fuse_nmon || !xt || n <= SINGLE_MAX) return false;
-    if (!(al16(x) && al16(h) && al16(hbar) && al16(v) && al16(xt) && al16(p1) && al16(p0) && al16(Ih) && al16(Ihb) &&
-          al16(Ir)))
-        return false;
-    const int np = parts_for(n);
-    T* parts_e = c->buf<T>("red_parts", MAX_PARTS);
-    double* parts_m = c->buf<double>("lsmr_mon_parts", MAX_PARTS);
-    if (first)
-        k_lsmr_step_mon<T, true><<<np, BS, 0, c->stream>>>(n, x, h, hbar, v, ssa, coef, st, k, xt, parts_e, p1, p0, Ih,
-                                                           Ihb, Ir, parts_m, cf);
-    else
-        k_lsmr_step_mon<T, false><<<np, BS, 0, c->stream>>>(n, x, h, hbar, v, ssa, coef, st, k, xt, parts_e, p1, p0, Ih,
-                                                            Ihb, Ir, parts_m, cf);
-    k_finalize<T><<<1, BS, 0, c->stream>>>(parts_e, np, err_out);
-    k_finalize<double><<<1, BS, 0, c->stream>>>(parts_m, np, mon_out);
-    HGM_HIP(hipGetLastError());
-    return true;
-}
-
-template <typename T>
-void lsmr_monitor(hgm_ctx* c, int64_t n, const T* p1, const T* p0, double c1, double c0, double* Ih, double* Ihb,
-                  double* Ix, const T* rhs, double f, double e, double cx, bool first, double* out, const double* cf) {
-    const int np = parts_for(n);
-    double* parts = c->buf<double>("lsmr_mon_parts", MAX_PARTS);
-    if (first)
-        k_lsmr_mon<T, true><<<np, BS, 0, c->stream>>>(n, p1, p0, c1, c0, Ih, Ihb, Ix, rhs, f, e, cx, parts, cf);
-    else
-        k_lsmr_mon<T, false><<<np, BS, 0, c->stream>>>(n, p1, p0, c1, c0, Ih, Ihb, Ix, rhs, f, e, cx, parts, cf);
-    k_finalize<double><<<1, BS, 0, c->stream>>>(parts, np, out);
+    // (no k_finalize: every block of k_vnorm re-forms the sum from the partials)
+    const SumParts<T> s = launch_sum<T>(c, n, SUM_ANY, "red_parts", nullptr, [&](auto vec, int np, T* parts) {
+        k_reduce_partial<T, 1, decltype(vec)::value><<<np, BS, 0, c->stream>>>(n, v, v, parts);
+    }, v);
+    k_vnorm<T><<<grid_for(n), BS, 0, c->stream>>>(n, v, s.parts, s.np, nrm_out);
     HGM_HIP(hipGetLastError());
 }
 
@@ -2227,23 +1497,6 @@ template <typename T> void convert_back(hgm_ctx* c, int64_t n, const T* in, doub
     template void cgs2<T>(hgm_ctx*, int64_t, T*, int64_t, int, T*, bool);                      \
     template void gemv<T>(hgm_ctx*, int64_t, int, const T*, int64_t, const T*, T*, int);       \
     template void div_scalar<T>(hgm_ctx*, int64_t, const T*, T*, T);                           \
-    template void lsqr_update<T>(hgm_ctx*, int64_t, T*, T*, const T*, T, T);                   \
-    template void lsqr_rot<T>(hgm_ctx*, const T*, const T*, double*, T*, double*, int, double, double,   \
-                              const ScalarCopy<T>&);                                            \
-    template void lsqr_step<T>(hgm_ctx*, int64_t, T*, T*, T*, const T*, const T*, const double*, int, const T*, T*); \
-    template void div_sqrt<T>(hgm_ctx*, int64_t, const T*, T*, const T*);                     \
-    template void lsmr_update<T>(hgm_ctx*, int64_t, T*, T*, T*, const T*, T, T, T, bool);      \
-    template void lsmr_monitor<T>(hgm_ctx*, int64_t, const T*, const T*, double, double, double*, double*, \
-                                  double*, const T*, double, double, double, bool, double*, const double*); \
-    template void lsmr_rot<T>(hgm_ctx*, const T*, const T*, double*, T*, double*, double*,         \
-                              const ScalarCopy<T>&);                                            \
-    template void lsmr_monitor_r<T>(hgm_ctx*, int64_t, const T*, const T*, T*, T*, T*, bool, double*, \
-                                    const double*);                                            \
-    template void lsmr_step<T>(hgm_ctx*, int64_t, T*, T*, T*, T*, const T*, const T*, const double*, int, \
-                               const T*, T*);                                                  \
-    template bool lsmr_step_mon<T>(hgm_ctx*, int64_t, T*, T*, T*, T*, const T*, const T*, const double*, int, \
-                                   const T*, T*, const T*, const T*, T*, T*, T*, bool, double*, const double*); \
-    template void div_sqrt_nz<T>(hgm_ctx*, int64_t, const T*, T*, const T*);                  \
     template void fill<T>(hgm_ctx*, int64_t, T*, T);                                           \
     template void scale<T>(hgm_ctx*, int64_t, const T*, T*, T);                                \
     template void fill_hash<T>(hgm_ctx*, int64_t, T*, uint64_t);                               \

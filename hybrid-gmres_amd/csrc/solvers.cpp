@@ -106,6 +106,95 @@ const FusedPlan* agreed_gk_plan(hgm_ctx* c, const hgm_mat* A, const hgm_mat* At,
     return fp;
 }
 
+// The one-pass Golub-Kahan step's arguments (internal.h FusedArgs): q = u, the row epilogue
+// v_hat = A'*u - beta*ev in place (beta^2 = *easq; ev == nullptr: the start, no epilogue), w = A*v_hat
+// into wm and ||v_hat||^2 = alpha^2 into wm[m], where it rides the m-vector all-reduce.
+template <typename T>
+FusedArgs<T> gk_pass_args(const T* u, T* ev, const T* easq, T* wm, int64_t m) {
+    FusedArgs<T> fa;
+    fa.q = u;
+    fa.ev = ev;
+    fa.easq = easq;
+    fa.zout = ev;
+    fa.w = wm;
+    fa.side_sq = true;
+    fa.side_out = wm + m;
+    return fa;
+}
+
+// Iterations enqueued ahead of the host: body(k) for k = 0, 1, ... in batches of `batch`; between
+// batches the host reads the device stop slot (stop_slot; nullptr: never), which holds iteration + 1
+// of the first stop, 0 while running.  body returns a stop the host itself found (iteration + 1), 0
+// to go on.  Returns the stop, 0 when all maxit iterations ran.
+template <typename F>
+int batched_iterations(hgm_ctx* c, int maxit, int batch, const double* stop_slot, F&& body) {
+    int stop = 0;
+    for (int k = 0; k < maxit && stop == 0;) {
+        const int kend = std::min(maxit, k + batch);
+        for (; k < kend && stop == 0; ++k) stop = body(k);
+        if (stop_slot && stop == 0) stop = (int)read1<double>(c, stop_slot);
+    }
+    return stop;
+}
+
+// Partial sums over the pixel shards that ride the NEXT iteration's m-vector all-reduce as its
+// trailing elements wm[m+1 ..] instead of taking a collective of their own: e, ||x - x_true||^2 into
+// errh[k], and d (fp64 only: a float element cannot carry the double sum), ||A'r||^2 into
+// monh[2k + 1].  The rotation kernel after that all-reduce copies the sums into iteration k's
+// history slots (ScalarCopy); the last iteration's are summed after the loop.
+template <typename T>
+struct Ridden {
+    T* base = nullptr;       // wm + m + 1; nullptr: nothing rides
+    int64_t n = 0;           // trailing elements past alpha^2
+    T *e = nullptr, *errh = nullptr;
+    double *d = nullptr, *monh = nullptr;
+    int last = -1;           // the last iteration enqueued
+    // the copies into iteration k's slots
+    ScalarCopy<T> into(int k) const {
+        ScalarCopy<T> cp;
+        if (e) {
+            cp.src = e;
+            cp.dst = errh + k;
+        }
+        if (d) {
+            cp.dsrc = d;
+            cp.ddst = monh + 2 * (size_t)k + 1;
+        }
+        return cp;
+    }
+    // elements of iteration k's m-vector all-reduce: [A*v_hat | alpha^2 | iteration k-1's sums]
+    int64_t count(int64_t m, int k) const { return (base && k > 0) ? m + 1 + n : m + 1; }
+};
+template <typename T>
+Ridden<T> ride_begin(hgm_ctx* c, bool ride, T* wm, int64_t m, T* errh, double* monh) {
+    Ridden<T> r;
+    if (!ride) return r;
+    r.base = wm + m + 1;
+    if (errh) r.e = r.base;
+    r.errh = errh;
+    if constexpr (std::is_same_v<T, double>)
+        if (monh) r.d = r.base + 1;
+    r.monh = monh;
+    r.n = r.d ? 2 : 1;
+    HGM_HIP(hipMemsetAsync(r.base, 0, sizeof(T) * r.n, c->stream));
+    return r;
+}
+template <typename T>
+void ride_end(hgm_ctx* c, const Ridden<T>& r) {
+    if (!r.base || r.last < 0) return;
+    allreduce(c, r.base, r.n);
+    copy_scalars<T>(c, r.into(r.last));
+}
+
+// res (:44) = |phi_bar| / ||b|| of iterations 0..k from the device history of phi_bar
+void read_phib(hgm_ctx* c, const double* phib, int maxit, int k, double nb, std::vector<double>& res) {
+    std::vector<double> pbh(maxit);
+    Reader rh(c);
+    rh.add(pbh.data(), phib, sizeof(double) * maxit);
+    rh.go();
+    for (int i = 0; i < maxit && i <= k; ++i) res[i] = std::fabs(pbh[i]) / nb;
+}
+
 // Input vector hand-over: device pointer (HGM_DEVICE_PTRS) or host buffer.
 template <typename T>
 const T* stage_in(hgm_ctx* c, const char* name, const double* p, int64_t n, bool dev) {
@@ -885,12 +974,8 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
     if (hybrid) {
         apply_B<T>(c, At, u, v, EPI_ADD, sq, un);                              // A_aug'*u_aug
     } else if (fp) {
-        FusedArgs<T> fa;                                                       // :10 v_hat = A'*u, A*v_hat
-        fa.q = u;
-        fa.zraw = v;
-        fa.w = wm;
-        fa.side_sq = true;
-        fa.side_out = wm + m;                                                  // ||v_hat||^2
+        FusedArgs<T> fa = gk_pass_args<T>(u, nullptr, nullptr, wm, m);          // :10 v_hat = A'*u, A*v_hat,
+        fa.zraw = v;                                                           //     ||v_hat||^2
         fused_pass<T>(c, At, fp, fa);
         if (dist_n(c)) allreduce(c, wm, m + 1);
     } else {
@@ -913,50 +998,40 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
     // iteration.  The host reads the stop flag once per batch of iterations (none when tol <= 0
     // cannot stop early); an iteration enqueued past the stop leaves x and w untouched.
     const bool dev_scalars = !fp && !hybrid && !parity && !dist_n(c) && c->num.lsqr_dev;
-    if (fp) {
-        // one pass per iteration, device-resident scalars (as below; on a communicator too: alpha^2
+    double c_x = 0, c_w = 0;                       // phi/rho, theta/rho of :40-41 (lsqr_rotate)
+    if (fp || dev_scalars) {
+        // (one pass per iteration: device-resident scalars as above, on a communicator too -- alpha^2
         // rides the m-vector all-reduce, beta^2 is a sum over the replicated m-vector)
         double* st = c->buf<double>("lsqr_st", 4);
         double* phib = c->buf<double>("lsqr_phib", maxit);
         T* coef = c->buf<T>("lsqr_coef", 2);
         const double st0[4] = {rho_bar, phi_bar, 0.0, 0.0};
         h2d(c, st, st0, sizeof(st0));
-        FusedArgs<T> fa;
-        fa.q = u;
-        fa.ev = v;                                 // v_k (divided by the previous lsqr_step)
-        fa.easq = sl + S_BETA;
-        fa.zout = v;                               // v_hat_{k+1} in place
-        fa.w = wm;
-        fa.side_sq = true;
-        fa.side_out = wm + m;
         // HGM_OPT_LSQR_DEV = 0: the same pass with host scalars -- beta^2 and alpha^2 read back per
         // iteration, the rotation and the stop test on the host in the same double arithmetic as
         // k_lsqr_rot (the coefficients uploaded for lsqr_step), so the iterates keep their bits
-        const bool host_sc = !c->num.lsqr_dev;
+        const bool host_sc = fp && !c->num.lsqr_dev;
         const int batch = tol > 0 && !host_sc ? 8 : maxit;
+        const double* stop_slot = host_sc ? nullptr : st + 2;
         int stop = 0;
-        // On a communicator the error partial ||x - x_true||^2 (:43, summed over the pixel shards)
-        // rides the NEXT iteration's m-vector all-reduce as element m+1, and the rotation kernel after
-        // that all-reduce copies the sum into the history: one collective per iteration instead of
-        // two (the stop test uses phi_bar, replicated).  The last iteration's partial is summed after
-        // the loop.
-        const bool ride = dist_n(c) && !host_sc;
-        T* ride_e = ride ? wm + m + 1 : nullptr;
-        if (ride) HGM_HIP(hipMemsetAsync(ride_e, 0, sizeof(T), c->stream));
-        int last = -1;
-        // the final residual (:52) from A*x kept alongside x (A*v_k is the pass's A*v_hat / alpha):
-        // no SpMV after the loop (HGM_OPT_LSQR_RES_IMG)
-        if (c->num.lsqr_res_img) {
-            img_ax = c->buf<double>("lsqr_ax", m + 1);
-            img_aw = c->buf<double>("lsqr_aw", m + 1);
-            lsqr_img<T>(c, m, wm, wm + m, coef, st, 0, img_ax, img_aw, true);
-        }
-        for (k = 0; k < maxit && stop == 0;) {
-            const int kend = std::min(maxit, k + batch);
-            for (; k < kend; ++k) {
+        if (fp) {
+            const FusedArgs<T> fa = gk_pass_args<T>(u, v, sl + S_BETA, wm, m);   // v_k in, v_hat_{k+1} in place
+            // On a communicator the error partial ||x - x_true||^2 (:43) rides the next iteration's
+            // m-vector all-reduce: one collective per iteration instead of two (the stop test uses
+            // phi_bar, replicated)
+            Ridden<T> rd = ride_begin<T>(c, dist_n(c) && !host_sc, wm, m, errh, nullptr);
+            // the final residual (:52) from A*x kept alongside x (A*v_k is the pass's A*v_hat / alpha):
+            // no SpMV after the loop (HGM_OPT_LSQR_RES_IMG)
+            if (c->num.lsqr_res_img) {
+                img_ax = c->buf<double>("lsqr_ax", m + 1);
+                img_aw = c->buf<double>("lsqr_aw", m + 1);
+                lsqr_img<T>(c, m, wm, wm + m, coef, st, 0, img_ax, img_aw, true);
+            }
+            stop = batched_iterations(c, maxit, batch, stop_slot, [&](int k) {
+                int host_stop = 0;
                 gkb_mstep_div<T>(c, m, wm, wm + m, u, t, nullptr, sl + S_BETA, false);   // :22-24
                 fused_pass<T>(c, At, fp, fa);                                        // :26-27 (+ A*v_hat)
-                if (dist_n(c)) allreduce(c, wm, (ride && k > 0) ? m + 2 : m + 1);
+                if (dist_n(c)) allreduce(c, wm, rd.count(m, k));
                 if (host_sc) {
                     T ss[2] = {T(0), T(0)};
                     Reader rr(c);
@@ -965,70 +1040,27 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
                     rr.go();
                     beta = std::sqrt((double)ss[0]);                                 // :23
                     alpha = std::sqrt((double)ss[1]);                                // :27
-                    const double rho = std::sqrt(rho_bar * rho_bar + beta * beta);   // :31-38
-                    const double cs = rho_bar / rho, sn = beta / rho;
-                    const double theta = sn * alpha;
-                    rho_bar = -cs * alpha;
-                    const double phi = cs * phi_bar;
-                    phi_bar = sn * phi_bar;
-                    const T cf[2] = {(T)(phi / rho), (T)(theta / rho)};
+                    lsqr_rotate(beta, alpha, rho_bar, phi_bar, c_x, c_w);            // :31-38
+                    const T cf[2] = {(T)c_x, (T)c_w};
                     h2d_pinned(c, coef, cf, sizeof(cf));    // the next Reader syncs past its use
                     res[k] = std::fabs(phi_bar) / nb;                                // :44
-                    if (res[k] <= tol) stop = k + 1;                                 // :46 (<=)
+                    if (res[k] <= tol) host_stop = k + 1;                            // :46 (<=)
                 } else {
-                    ScalarCopy<T> cp;
-                    if (ride && k > 0) {
-                        cp.src = ride_e;
-                        cp.dst = errh + k - 1;
-                    }
-                    lsqr_rot<T>(c, sl + S_BETA, wm + m, st, coef, phib, k, nb, tol, cp);   // :31-38, :44-46
+                    lsqr_rot<T>(c, sl + S_BETA, wm + m, st, coef, phib, k, nb, tol,  // :31-38, :44-46
+                                k > 0 ? rd.into(k - 1) : ScalarCopy<T>{});
                 }
-                lsqr_step<T>(c, n, x, w, v, wm + m, coef, st, k, xt, ride ? ride_e : errh + k);   // :28, :40-41, :43
-                last = k;
+                lsqr_step<T>(c, n, x, w, v, wm + m, coef, st, k, xt, rd.e ? rd.e : errh + k);   // :28, :40-41, :43
+                rd.last = k;
                 if (img_ax) lsqr_img<T>(c, m, wm, wm + m, coef, st, k, img_ax, img_aw, false);
-                if (dist_n(c) && !ride) allreduce(c, errh + k, 1);
-                if (stop) {
-                    ++k;
-                    break;
-                }
-            }
-            if (host_sc) continue;
-            double sv = 0;
-            Reader rs(c);
-            rs.add(&sv, st + 2, sizeof(double));
-            rs.go();
-            stop = (int)sv;
-        }
-        if (ride && last >= 0) {                       // the last iteration's error partial
-            allreduce(c, ride_e, 1);
-            ScalarCopy<T> cp;
-            cp.src = ride_e;
-            cp.dst = errh + last;
-            copy_scalars<T>(c, cp);
-        }
-        k = stop > 0 ? stop - 1 : maxit;
-        if (!host_sc) {
-            std::vector<double> pbh(maxit);
-            Reader rh(c);
-            rh.add(pbh.data(), phib, sizeof(double) * maxit);
-            rh.go();
-            for (int i = 0; i < maxit && i <= k; ++i) res[i] = std::fabs(pbh[i]) / nb;   // :44
-        }
-    }
-    if (dev_scalars) {
-        double* st = c->buf<double>("lsqr_st", 4);
-        double* phib = c->buf<double>("lsqr_phib", maxit);
-        T* coef = c->buf<T>("lsqr_coef", 2);
-        const double st0[4] = {rho_bar, phi_bar, 0.0, 0.0};
-        h2d(c, st, st0, sizeof(st0));
-        PendNorm<T> pa, pb;
-        pa.asq = sl + S_ALPHA;                     // A*v - alpha*u
-        pb.asq = sl + S_BETA;                      // A'*u - beta*v
-        const int batch = tol > 0 ? 8 : maxit;
-        int stop = 0;
-        for (k = 0; k < maxit && stop == 0;) {
-            const int kend = std::min(maxit, k + batch);
-            for (; k < kend; ++k) {
+                if (dist_n(c) && !rd.e) allreduce(c, errh + k, 1);
+                return host_stop;
+            });
+            ride_end(c, rd);
+        } else {
+            PendNorm<T> pa, pb;
+            pa.asq = sl + S_ALPHA;                     // A*v - alpha*u
+            pb.asq = sl + S_BETA;                      // A'*u - beta*v
+            stop = batched_iterations(c, maxit, batch, stop_slot, [&](int k) {
                 spmv<T>(c, A, v, t, EPI_SUB, T(0), u, KC_SPMV_A, nullptr, &pa);     // :22
                 sumsq<T>(c, m, t, sl + S_BETA);                                      // :23
                 div_sqrt<T>(c, m, t, u, sl + S_BETA);                                // :24
@@ -1036,19 +1068,11 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
                 sumsq<T>(c, n, v, sl + S_ALPHA);                                     // :27
                 lsqr_rot<T>(c, sl + S_BETA, sl + S_ALPHA, st, coef, phib, k, nb, tol);   // :31-38, :44-46
                 lsqr_step<T>(c, n, x, w, v, sl + S_ALPHA, coef, st, k, xt, errh + k);     // :28, :40-41, :43
-            }
-            double sv = 0;
-            Reader rs(c);
-            rs.add(&sv, st + 2, sizeof(double));
-            rs.go();
-            stop = (int)sv;
+                return 0;
+            });
         }
         k = stop > 0 ? stop - 1 : maxit;
-        std::vector<double> pbh(maxit);
-        Reader rh(c);
-        rh.add(pbh.data(), phib, sizeof(double) * maxit);
-        rh.go();
-        for (int i = 0; i < maxit && i <= k; ++i) res[i] = std::fabs(pbh[i]) / nb;   // :44
+        if (!host_sc) read_phib(c, phib, maxit, k, nb, res);                         // :44
     }
     for (; !dev_scalars && !fp && k < maxit; ++k) {
         // :22-24  u_hat = A*v - alpha*u ; beta = norm(u_hat) ; u = u_hat / beta
@@ -1088,15 +1112,8 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
         nsumsq<T>(c, n, v, sl + S_ALPHA);
         alpha = std::sqrt((double)read1<T>(c, sl + S_ALPHA));                 // :27
         div_scalar<T>(c, n, v, v, (T)alpha);                                   // :28
-        // :31-38 Givens rotation (host scalars)
-        const double rho = std::sqrt(rho_bar * rho_bar + beta * beta);
-        const double cs = rho_bar / rho;
-        const double sn = beta / rho;
-        const double theta = sn * alpha;
-        rho_bar = -cs * alpha;
-        const double phi = cs * phi_bar;
-        phi_bar = sn * phi_bar;
-        lsqr_update<T>(c, n, x, w, v, (T)(phi / rho), (T)(theta / rho));     // :40-41
+        lsqr_rotate(beta, alpha, rho_bar, phi_bar, c_x, c_w);                  // :31-38 (host scalars)
+        lsqr_update<T>(c, n, x, w, v, (T)c_x, (T)c_w);                         // :40-41
         nsumsq_diff<T>(c, n, x, xt, hybrid ? sl + S_ERR : errh + k);
         if (hybrid) {
             apply_A<T>(c, A, x, t, EPI_RSUB, T(0), b);                        // hybrid :43  b - A*x
@@ -1237,12 +1254,8 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
     if (beta > 0) div_scalar<T>(c, m, u, u, (T)beta);                          // :12
     T* v0 = kept ? Atu0 : v;                                                   // raw A'*u_0 kept
     if (fp) {
-        FusedArgs<T> fa;                                                       // :14 (+ A*v_hat, ||v_hat||^2)
-        fa.q = u;
+        FusedArgs<T> fa = gk_pass_args<T>(u, nullptr, nullptr, wm, m);          // :14 (+ A*v_hat, ||v_hat||^2)
         fa.zraw = v0;
-        fa.w = wm;
-        fa.side_sq = true;
-        fa.side_out = wm + m;
         fused_pass<T>(c, At, fp, fa);
         if (dist_n(c)) allreduce(c, wm, m + 1);
     } else {
@@ -1255,9 +1268,10 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
     if (kept) scale<T>(c, n, Atu0, Atb, (T)beta);
     if (alpha > 0) div_scalar<T>(c, n, v0, v, (T)alpha);                       // :16
     else if (kept) HGM_HIP(hipMemcpyAsync(v, v0, sizeof(T) * n, hipMemcpyDeviceToDevice, c->stream));
-    double zetabar = alpha * beta, alphabar = alpha, rho = 1, rhobar = 1, cbar = 1, sbar = 0;   // :19-23
+    // The rotations' state (lsmr_rotate, internal.h): [alpha, alphabar, rho, rhobar, cbar, sbar, zetabar
+    // = alpha*beta (:19-23), theta/rho of the previous :67, the device loop's stop slot]
+    double rot[9] = {alpha, alpha, 1, 1, 1, 0, alpha * beta, 0.0, 0.0};
     HGM_HIP(hipMemcpyAsync(h, v, sizeof(T) * n, hipMemcpyDeviceToDevice, c->stream));   // :25
-    double prev_ch = 0.0;                                                      // (theta/rho) of the previous :67
     // tol <= 0: `res < tol` (:76) can never hold, so the monitors stay on the device and are
     // read once after the loop instead of once per iteration
     // (and with the device-resident scalars below at any tol)
@@ -1292,109 +1306,50 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
         double* cfm = c->buf<double>("lsmr_cf", 10);
         double* cfn = cfm + 5;
         T* coef = c->buf<T>("lsmr_coef", 3);
-        const double st0[9] = {alpha, alphabar, rho, rhobar, cbar, sbar, zetabar, 0.0, 0.0};
-        h2d(c, st, st0, sizeof(st0));
-        FusedArgs<T> fa;
-        fa.q = u;
-        fa.ev = v;
-        fa.easq = sl + S_BETA;
-        fa.zout = v;
-        fa.w = wm;
-        fa.side_sq = true;
-        fa.side_out = wm + m;
-        const int batch = tol > 0 ? 8 : maxit;
-        int stop = 0;
+        h2d(c, st, rot, sizeof(rot));
+        FusedArgs<T> fa = gk_pass_args<T>(u, v, sl + S_BETA, wm, m);
         // On a communicator the n-space partials of iteration k -- ||x - x_true||^2 (:72) and, in
-        // fp64, ||A'r||^2 (:71) -- ride iteration k+1's m-vector all-reduce as elements m+1, m+2, and
-        // the rotation kernel copies the sums into the histories: one collective per iteration
-        // instead of three (fp32: two; its ||A'r||^2 is a double sum that a float element cannot
-        // carry).  The stop test (:76) reads only the replicated m-space residual.  The last
-        // iteration's partials are summed after the loop.
-        constexpr bool ride_d_ok = std::is_same_v<T, double>;
-        const bool ride = dist_n(c);
-        T* ride_e = (ride && xt) ? wm + m + 1 : nullptr;
-        double* ride_d = nullptr;
-        if constexpr (ride_d_ok)
-            if (ride) ride_d = reinterpret_cast<double*>(wm + m + 2);
-        const int64_t ride_n = ride_d ? 2 : 1;       // trailing elements past alpha^2
-        if (ride) HGM_HIP(hipMemsetAsync(wm + m + 1, 0, sizeof(T) * ride_n, c->stream));
-        int last = -1;
-        for (k = 0; k < maxit && stop == 0;) {
-            const int kend = std::min(maxit, k + batch);
-            for (; k < kend; ++k) {
-                gkb_mstep_div<T>(c, m, wm, wm + m, u, r, Av, sl + S_BETA, true);  // :34-36 (+ kept A*v_k)
-                fa.zraw = Atu1;                                                   // A'*u_{k+1} (kept)
-                fused_pass<T>(c, At, fp, fa);                                     // :38-39 (+ A*v_hat)
-                if (dist_n(c)) allreduce(c, wm, (ride && k > 0) ? m + 1 + ride_n : m + 1);
-                ScalarCopy<T> cp;
-                if (ride && k > 0) {
-                    if (ride_e) {
-                        cp.src = ride_e;
-                        cp.dst = errh + k - 1;
-                    }
-                    if (ride_d) {
-                        cp.dsrc = ride_d;
-                        cp.ddst = dmonh + 2 * (size_t)(k - 1) + 1;
-                    }
-                }
-                lsmr_rot<T>(c, sl + S_BETA, wm + m, st, coef, cfm, cfn, cp);      // :42-67 scalars
-                double* dm = dmonh + 2 * (size_t)k;
-                T* e_out = xt ? (ride_e ? ride_e : errh + k) : nullptr;
-                double* d_out = ride_d ? ride_d : dm + 1;
-                // (fp32: the n-space step and the n-space monitor in one launch when it applies)
-                const bool nmon = img_t && lsmr_step_mon<T>(c, n, x, h, hbar, v, wm + m, coef, st, k, xt, e_out,
-                                                            Atu1, Atu0, Ihn_t, Ihbn_t, Irn_t, k == 0, d_out, cfn);
-                if (!nmon) lsmr_step<T>(c, n, x, h, hbar, v, wm + m, coef, st, k, xt, e_out);   // :40, :61-67, :72
-                last = k;
-                if (xt && dist_n(c) && !ride_e) allreduce(c, errh + k, 1);
-                lsmr_monitor<T>(c, m, Av, nullptr, 0, 0, Ihm, Ihbm, Ixm, b, 0, 0, 0, k == 0, dm, cfm);
-                if (!nmon && img_t) lsmr_monitor_r<T>(c, n, Atu1, Atu0, Ihn_t, Ihbn_t, Irn_t, k == 0, d_out, cfn);
-                else if (!nmon) lsmr_monitor<T>(c, n, Atu1, Atu0, 0, 0, Ihn, Ihbn, Ixn, Atb, 0, 0, 0, k == 0, d_out, cfn);
-                if (dist_n(c) && !ride_d) allreduce(c, dm + 1, 1);
-                std::swap(Atu0, Atu1);
-                if (tol > 0) lsmr_stop(c, dm, nb, tol, st, k);                   // :76
-            }
-            if (tol > 0) {
-                double sv = 0;
-                Reader rs(c);
-                rs.add(&sv, st + 8, sizeof(double));
-                rs.go();
-                stop = (int)sv;
-            }
-        }
-        if (ride && last >= 0) {                       // the last iteration's ridden partials
-            allreduce(c, wm + m + 1, ride_n);
-            ScalarCopy<T> cp;
-            if (ride_e) {
-                cp.src = ride_e;
-                cp.dst = errh + last;
-            }
-            if (ride_d) {
-                cp.dsrc = ride_d;
-                cp.ddst = dmonh + 2 * (size_t)last + 1;
-            }
-            copy_scalars<T>(c, cp);
-        }
+        // fp64, ||A'r||^2 (:71) -- ride iteration k+1's m-vector all-reduce: one collective per
+        // iteration instead of three (fp32: two).  The stop test (:76) reads only the replicated
+        // m-space residual.
+        Ridden<T> rd = ride_begin<T>(c, dist_n(c), wm, m, xt ? errh : nullptr, dmonh);
+        const int stop = batched_iterations(c, maxit, tol > 0 ? 8 : maxit, tol > 0 ? st + 8 : nullptr, [&](int k) {
+            gkb_mstep_div<T>(c, m, wm, wm + m, u, r, Av, sl + S_BETA, true);  // :34-36 (+ kept A*v_k)
+            fa.zraw = Atu1;                                                   // A'*u_{k+1} (kept)
+            fused_pass<T>(c, At, fp, fa);                                     // :38-39 (+ A*v_hat)
+            if (dist_n(c)) allreduce(c, wm, rd.count(m, k));
+            lsmr_rot<T>(c, sl + S_BETA, wm + m, st, coef, cfm, cfn,           // :42-67 scalars
+                        k > 0 ? rd.into(k - 1) : ScalarCopy<T>{});
+            double* dm = dmonh + 2 * (size_t)k;
+            T* e_out = xt ? (rd.e ? rd.e : errh + k) : nullptr;
+            double* d_out = rd.d ? rd.d : dm + 1;
+            // (fp32: the n-space step and the n-space monitor in one launch when it applies)
+            const bool nmon = img_t && lsmr_step_mon<T>(c, n, x, h, hbar, v, wm + m, coef, st, k, xt, e_out,
+                                                        Atu1, Atu0, Ihn_t, Ihbn_t, Irn_t, k == 0, d_out, cfn);
+            if (!nmon) lsmr_step<T>(c, n, x, h, hbar, v, wm + m, coef, st, k, xt, e_out);   // :40, :61-67, :72
+            rd.last = k;
+            if (xt && dist_n(c) && !rd.e) allreduce(c, errh + k, 1);
+            lsmr_monitor<T>(c, m, Av, nullptr, 0, 0, Ihm, Ihbm, Ixm, b, 0, 0, 0, k == 0, dm, cfm);
+            if (!nmon && img_t) lsmr_monitor_r<T>(c, n, Atu1, Atu0, Ihn_t, Ihbn_t, Irn_t, k == 0, d_out, cfn);
+            else if (!nmon) lsmr_monitor<T>(c, n, Atu1, Atu0, 0, 0, Ihn, Ihbn, Ixn, Atb, 0, 0, 0, k == 0, d_out, cfn);
+            if (dist_n(c) && !rd.d) allreduce(c, dm + 1, 1);
+            std::swap(Atu0, Atu1);
+            if (tol > 0) lsmr_stop(c, dm, nb, tol, st, k);                   // :76
+            return 0;
+        });
+        ride_end(c, rd);
         k = stop > 0 ? stop - 1 : maxit;
     }
     for (k = dev_scalars ? k : 0; !dev_scalars && k < maxit; ++k) {
-        const double alpha_k = alpha;
         if (fp) {
             // :34 A*v_k = (A*v_hat)/alpha_k (kept), u = A*v - alpha*u, ||u||^2
             gkb_mstep<T>(c, m, wm, wm + m, u, r, kept ? Av : nullptr, sl + S_BETA);
             beta = std::sqrt((double)read1<T>(c, sl + S_BETA));               // :35
             if (beta > 0) div_scalar<T>(c, m, r, u, (T)beta);                  // :36
             else HGM_HIP(hipMemcpyAsync(u, r, sizeof(T) * m, hipMemcpyDeviceToDevice, c->stream));
-            FusedArgs<T> fa;                                                   // :38 v = A.'*u - beta*v, one pass
-            fa.q = u;
+            FusedArgs<T> fa = gk_pass_args<T>(u, v, sl + S_BETA, wm, m);       // :38 v = A.'*u - beta*v, one pass
             fa.zraw = kept ? Atu1 : nullptr;                                   // A'*u_{k+1} (kept)
-            fa.ev = v;
-            fa.easq = sl + S_BETA;
-            fa.zout = v;
-            fa.w = wm;
-            fa.side_sq = true;
-            fa.side_out = wm + m;                                              // ||v||^2 (:39)
-            fused_pass<T>(c, At, fp, fa);
+            fused_pass<T>(c, At, fp, fa);                                      // (+ ||v||^2, :39)
             if (dist_n(c)) allreduce(c, wm, m + 1);
             alpha = std::sqrt((double)read1<T>(c, wm + m));                    // :39
         } else {
@@ -1417,30 +1372,16 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
             alpha = std::sqrt((double)read1<T>(c, sl + S_ALPHA));             // :39
         }
         if (alpha > 0) div_scalar<T>(c, n, v, v, (T)alpha);                    // :40
-        const double alphahat = alphabar;                                      // :42
-        const double rhoold = rho;                                             // :43
-        rho = std::hypot(alphahat, beta);                                      // :44
-        const double cc = alphahat / rho, ss = beta / rho;                     // :45-46
-        const double thetanew = ss * alpha;                                    // :48
-        alphabar = cc * alpha;                                                 // :49
-        const double rhobarold = rhobar;                                       // :51
-        const double thetabar = sbar * rho;                                    // :52
-        rhobar = std::hypot(cbar * rho, thetanew);                             // :53
-        cbar = (cbar * rho) / rhobar;                                          // :54
-        sbar = thetanew / rhobar;                                              // :55
-        const double zeta = cbar * zetabar;                                    // :58
-        zetabar = -sbar * zetabar;                                             // :59
-        const double c_hbar = (thetabar * rho) / (rhoold * rhobarold);         // :64
-        const double c_x = zeta / (rho * rhobar);                              // :66
-        const double c_h = thetanew / rho;                                     // :67
-        lsmr_update<T>(c, n, x, h, hbar, v, (T)c_hbar, (T)c_x, (T)c_h, k == 0);
+        double cf[3], cfm[5], cfn[5];                  // [c_hbar, c_x, c_h]; the monitors' [c1, c0, f, e, cx]
+        lsmr_rotate(beta, alpha, rot, cf, cfm, cfn);                           // :42-67 scalars
+        lsmr_update<T>(c, n, x, h, hbar, v, (T)cf[0], (T)cf[1], (T)cf[2], k == 0);   // :61-67
         double mon[2] = {0.0, 0.0};
         Reader rr(c);
         if (kept) {
             // :69 ||b - A*x||^2 and :71 ||A'b - A'A*x||^2 from the kept images
             double* dm = defer_mon ? dmonh + 2 * (size_t)k : dmon;
-            lsmr_monitor<T>(c, m, Av, nullptr, 1.0, 0.0, Ihm, Ihbm, Ixm, b, prev_ch, c_hbar, c_x, k == 0, dm);
-            lsmr_monitor<T>(c, n, Atu1, Atu0, beta, alpha_k, Ihn, Ihbn, Ixn, Atb, prev_ch, c_hbar, c_x, k == 0,
+            lsmr_monitor<T>(c, m, Av, nullptr, cfm[0], cfm[1], Ihm, Ihbm, Ixm, b, cfm[2], cfm[3], cfm[4], k == 0, dm);
+            lsmr_monitor<T>(c, n, Atu1, Atu0, cfn[0], cfn[1], Ihn, Ihbn, Ixn, Atb, cfn[2], cfn[3], cfn[4], k == 0,
                             dm + 1);
             if (dist_n(c)) allreduce(c, dm + 1, 1);
             std::swap(Atu0, Atu1);
@@ -1453,7 +1394,6 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
             rr.add(&hs[0], sl + S_RES, sizeof(T));
             rr.add(&hs[1], sl + S_AR, sizeof(T));
         }
-        prev_ch = c_h;
         if (xt) nsumsq_diff<T>(c, n, x, xt, defer_mon ? errh + k : sl + S_ERR);
         if (defer_mon) continue;
         if (xt) rr.add(&hs[2], sl + S_ERR, sizeof(T));

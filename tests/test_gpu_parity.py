@@ -644,13 +644,15 @@ def test_mgs_one_reduction_form(gpu_ctx, N, na, maxit):
 
 
 @pytest.mark.parametrize("N,na,dtype,stop", [(64, 90, "f64", False), (64, 90, "f64", True), (512, 30, "f64", True),
-                                             (512, 30, "f32", False), (24, 12, "f64", True)])
+                                             (512, 30, "f32", False), (24, 12, "f64", True),
+                                             (183, 12, "f32", True), (183, 12, "f64", False)])
 def test_lsqr_device_scalars_are_bitwise(gpu_ctx, N, na, dtype, stop):
     """HGM_OPT_LSQR_DEV (default): beta, alpha, the Givens rotation and the stop test of
     lsqr_solver.m:22-46 on the device (SpMV epilogues read the coefficients there) give bitwise
     the host-driven loop's x and histories -- including a `tol` stop mid-batch (the iterations
-    enqueued past it must leave x alone), fp32, and a vector short enough for the one-launch
-    error reduction."""
+    enqueued past it must leave x alone), fp32, a vector short enough for the one-launch
+    error reduction, and n = 183^2 = 33489 (odd, just above the one-launch limit: the fused
+    error sum's 16-byte vectors leave a tail)."""
     P = tomo_problem(N, na, noise=1e-2, seed=0)
     dt = hgmres._lib.HGM_F32 if dtype == "f32" else hgmres._lib.HGM_F64
     A = hgmres.SparseOperator.from_scipy(P.A, gpu_ctx, dtype=dt)
