@@ -594,6 +594,10 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
             if (!(v == 0 || v == 1 || v == 2 || v == 3 || v == 4)) return bad("fused_rowpair is 0 to 4");
             n.fused_rowpair = (int)v;
             break;
+        case HGM_OPT_FUSED_VSTREAM:
+            if (!(v == 0 || v == 1 || v == 2 || v == 3)) return bad("fused_vstream is 0 to 3");
+            n.fused_vstream = (int)v;
+            break;
         case HGM_OPT_LSQR_RES_IMG: if (!b01) return bad("lsqr_res_img is 0 or 1"); n.lsqr_res_img = v != 0; break;
         case HGM_OPT_LSMR_FUSE_NMON: if (!b01) return bad("lsmr_fuse_nmon is 0 or 1"); n.lsmr_fuse_nmon = v != 0; break;
         case HGM_OPT_HOST_SPIN_US:
@@ -642,6 +646,7 @@ HGM_API int hgm_ctx_get_option(const hgm_ctx* c, int option, double* v) {
         case HGM_OPT_FUSED_PLAN_DEV: *v = n.fused_plan_dev; break;
         case HGM_OPT_FUSED_REDUCE: *v = n.fused_reduce; break;
         case HGM_OPT_FUSED_ROWPAIR: *v = n.fused_rowpair; break;
+        case HGM_OPT_FUSED_VSTREAM: *v = n.fused_vstream; break;
         case HGM_OPT_LSQR_RES_IMG: *v = n.lsqr_res_img; break;
         case HGM_OPT_LSMR_FUSE_NMON: *v = n.lsmr_fuse_nmon; break;
         case HGM_OPT_HOST_SPIN_US: *v = g_host_spin_us.load(); break;
@@ -699,8 +704,9 @@ HGM_API int hgm_ctx_solve_path(const hgm_ctx* c, int what, int* out, int cap, in
 }
 
 // ---- matrices ----------------------------------------------------------------
-HGM_API int hgm_mat_create_csr(hgm_ctx* c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* row_ptr,
-                               const int32_t* col_idx, const double* val, int dtype, hgm_mat** out) {
+static int create_csr_impl(hgm_ctx* c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* row_ptr,
+                           const int32_t* col_idx, const double* val, int dtype, const hgm::PixOrder& col_order,
+                           hgm_mat** out) {
     if (!c || !out || rows < 0 || cols < 0 || nnz < 0 || !row_ptr || (nnz > 0 && (!col_idx || !val)))
         return HGM_E_ARG;
     if (dtype != HGM_F64 && dtype != HGM_F32) return HGM_E_ARG;
@@ -725,10 +731,29 @@ HGM_API int hgm_mat_create_csr(hgm_ctx* c, int64_t rows, int64_t cols, int64_t n
             }
         }
         HGM_HIP(hipStreamSynchronize(c->stream));
+        M->col_order = col_order;
         finalize_operator(c, M);
     });
     *out = M;
     return HGM_OK;
+}
+
+HGM_API int hgm_mat_create_csr(hgm_ctx* c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* row_ptr,
+                               const int32_t* col_idx, const double* val, int dtype, hgm_mat** out) {
+    return create_csr_impl(c, rows, cols, nnz, row_ptr, col_idx, val, dtype, hgm::PixOrder{}, out);
+}
+
+HGM_API int hgm_mat_create_csr_tiled(hgm_ctx* c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* row_ptr,
+                                     const int32_t* col_idx, const double* val, int dtype, int N, int tile,
+                                     int super_block, hgm_mat** out) {
+    if (!c) return HGM_E_ARG;
+    if (N <= 0 || (int64_t)N * N != cols || tile < 1 || N % tile || super_block < 0 ||
+        (super_block > 1 && (N % super_block || super_block % tile))) {
+        c->err = "hgm_mat_create_csr_tiled: the columns are the pixels of an N x N image, tile | N, tile | super_block | N";
+        return HGM_E_ARG;
+    }
+    const hgm::PixOrder o = (tile > 1 || super_block > 1) ? hgm::PixOrder{N, tile, super_block} : hgm::PixOrder{};
+    return create_csr_impl(c, rows, cols, nnz, row_ptr, col_idx, val, dtype, o, out);
 }
 
 HGM_API int hgm_mat_create_csc(hgm_ctx* c, int64_t rows, int64_t cols, int64_t nnz, const int64_t* jc,
@@ -1068,6 +1093,17 @@ HGM_API int hgm_fused_plan_info(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, 
         if (checksum) *checksum = fused_plan_checksum(c, B, P);
         if (nslot) *nslot = fused_plan_slots(P);
         if (device_built) *device_built = fused_plan_device_built(P) ? 1 : 0;
+    });
+    return HGM_OK;
+}
+
+HGM_API int hgm_fused_vstream_info(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, int* active, double* coverage,
+                                   int64_t* value_bytes, int64_t* plan_bytes) {
+    if (!c || !A || !B) return HGM_E_ARG;
+    HGM_TRY(c, {
+        const FusedPlan* P = fused_ab_plan(c, A, B);
+        HGM_REQUIRE(P != nullptr, "fused plan: this pair has none (two-pass path)");
+        fused_plan_vstream_info(P, active, coverage, value_bytes, plan_bytes);
     });
     return HGM_OK;
 }

@@ -25,6 +25,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <chrono>
 #include <numeric>
 #include <thread>
@@ -90,6 +91,16 @@ struct FusedPlan {
     double* zx_part = nullptr;    // kind 1: nreg (the regions' side sums; fp32 plans: float)
     double build_s = 0;
     bool dev_built = false;       // kind 1: ray sets built on the device (HGM_OPT_FUSED_PLAN_DEV)
+    // kind 1, fp64 row-pair mode 4: the compact value stream (HGM_OPT_FUSED_VSTREAM, k_fused_rw RP 5;
+    // "Compact value stream" below).  lidx stays: the Golub-Kahan form of the pass reads the plain streams.
+    bool vs_on = false;           // the pass reads the compact streams
+    int64_t nunit = 0, vs_pairs = 0, vs_coded = 0;   // units, 16-byte value pairs, entries with a code
+    int64_t nnz = 0, nwrun = 0;                      // B's entries, the row runs of `runs`
+    uint2* vs_desc = nullptr;     // nunit + 1: (first value pair, first-row entries | first-row coded pairs << 8)
+    int32_t* vs_run_unit = nullptr;   // per run of `runs`: its first unit
+    double* vs_table = nullptr;   // 32: entry 31 - c = the value of code c (code 0: -0.0)
+    uint32_t* vs_slots = nullptr; // 64 words per unit: lane l's two slots and codes
+    double* vs_vals = nullptr;    // 2 * vs_pairs
 };
 
 void fused_plan_free(FusedPlan* P) {
@@ -97,7 +108,8 @@ void fused_plan_free(FusedPlan* P) {
     for (void* p : {(void*)P->reg_sub, (void*)P->reg_base, (void*)P->subs, (void*)P->perm, (void*)P->lr_ray,
                     (void*)P->lr_pk, (void*)P->rs_ptr, (void*)P->rs_slot, (void*)P->part, (void*)P->wrun,
                     (void*)P->runs, (void*)P->ray_tab, (void*)P->lidx, (void*)P->zx_part, (void*)P->band_ptr,
-                    (void*)P->band_run})
+                    (void*)P->band_run, (void*)P->vs_desc, (void*)P->vs_run_unit, (void*)P->vs_table,
+                    (void*)P->vs_slots, (void*)P->vs_vals})
         if (p) (void)hipFree(p);
     delete P;
 }
@@ -625,6 +637,32 @@ template <> struct AccT<float, 2> { using t = double; };
 // RP = 2 places the second row at its own pair-aligned start on the lane after the first row's last
 // pair (row membership per lane, not per entry: fewer instructions per unit); a unit then fits when
 // the two rows' pair counts add up to <= 64 lanes.
+// RP = 5 (compact value stream, HGM_OPT_FUSED_VSTREAM; fp64, GK = false) is RP 4 reading plan-owned
+// streams instead of B's values, the plan's lidx and B's row pointers.  The up to 31 most frequent
+// value bit patterns of the operator are CODES; only the other values (ESCAPES) are stored.  A unit's
+// entries are reordered at plan time into
+//     [first row coded | first row escapes | second row escapes | second row coded]  (<= 128),
+// so an entry belongs to the first row iff its position is below the first row's length (one
+// compare, no unit offset), and the escapes are one contiguous stretch:
+//   slots   64 words per unit, lane l's word = positions 2l, 2l+1: slot offsets in bits 3-13 and 19-29,
+//           the code of 2l in bits 14-18, of 2l+1 in bits 30-31 (low) and 0-2 (high); positions past
+//           the unit carry their lane's dummy slot and code 0, so the kernel needs no "inside" test;
+//   values  the escapes as 16-byte pairs: pair j = positions 2 (c0h + j), +1 with c0h = (first row's
+//           coded) / 2; a position that is not an escape holds 0.0;
+//   descriptor (8 B per unit, instead of the row pointers): first value pair, first row's entries,
+//           c0h; the next unit's first pair ends this one's.
+// Decode without a select: v = loaded + table[code] with table[0] = -0.0 (x + -0.0 = x for every x,
+// -0.0 included) and loaded = 0.0 wherever the entry is coded (0.0 + t = t for the finite non-zero
+// t the dictionary holds): bit for bit the stored value.  The table sits in the q slots below the
+// dummies, code c at slot MAXR - 65 - c (the word's 5-bit field holds 31 - c, so the offset is an
+// immediate plus field * 8); the plan keeps as many codes as the fullest region leaves slots for
+// (rays <= MAXR - 65 - codes; C4: 1,924 rays in 1,984 ray slots, all 31 codes).
+struct VStream {
+    const uint2* desc = nullptr;
+    const int32_t* run_unit = nullptr;
+    const double* table = nullptr;
+};
+
 template <typename T, bool GK, int AM, int W, int MAXR, int G, int NCH, int D, bool PR, int DBG = 0, int RP = 0>
 __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__ reg_base, const int32_t* __restrict__ ray_tab,
                                                      const int32_t* __restrict__ wrun, const int2* __restrict__ runs,
@@ -633,9 +671,12 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
                                                      T* __restrict__ zraw, typename AccT<T, AM>::t* __restrict__ part,
                                                      const T* __restrict__ xt, T* __restrict__ zx_part,
                                                      const T* ev, const T* __restrict__ easq, T* zout, int side_sq,
-                                                     PendNorm<T> pn) {
+                                                     PendNorm<T> pn, VStream vs) {
     static_assert(D >= 2 && D <= 4, "ring depth");
     static_assert(!RP || (PR && NCH == 1 && DBG == 0 && G % 2 == 0), "row pairs: pairs, one chunk");
+    constexpr bool VS = RP == 5;                 // compact value stream: val = the escapes, lidx = the unit words
+    static_assert(!VS || (sizeof(T) == 8 && !GK && AM == 0 && MAXR <= 2048 && G == 8), "compact value stream: fp64 GMRES form");
+    constexpr int VTAB = MAXR - 96;              // (VS) the code table's first q slot
     constexpr int NA = (RP == 1 || RP == 2) ? 2 : 1;   // private accumulator arrays per wave
     using TA = typename AccT<T, AM>::t;
     constexpr int EPL = PR ? 2 : 1;              // entries per lane per chunk
@@ -664,6 +705,12 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
     const int ub = wrun[g * W + wv + 1];
     const int2 runv = __builtin_bit_cast(
         int2, __builtin_amdgcn_raw_buffer_load_b64(buf_rsrc(runs + ua, (ub - ua) * 8), ln * 8, 0, 0));
+    int runu = 0;                                // (VS) the first unit of each of the wave's runs
+    T tabv = T(0);                               // (VS) the code table, entry threadIdx.x of 32
+    if constexpr (VS) {
+        runu = (int)__builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(vs.run_unit + ua, (ub - ua) * 4), ln * 4, 0, 0);
+        tabv = (T)vs.table[threadIdx.x & 31];
+    }
     static_assert(BS == 256 && MAX_PARTS <= 4 * BS, "pending-normalisation sum: four virtual waves");
     T hq = T(0);
     auto pend_h = [&]() -> T {
@@ -736,6 +783,10 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
             }
         }
         if (threadIdx.x < 64) qloc[MAXR - 64 + threadIdx.x] = T(0);
+        if constexpr (VS) {
+            // (entries below the plan's codes are unused: those slots may hold rays)
+            if (threadIdx.x < 32 && VTAB + (int)threadIdx.x >= nr) qloc[VTAB + threadIdx.x] = tabv;
+        }
     };
     // the epilogue coefficient: the bits the host takes from the same sum of squares
     const T ea = (GK && easq) ? (T)sqrt((double)*easq) : T(0);
@@ -744,11 +795,13 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
     TA* __restrict__ ac = &acc[wv][0][0];
     constexpr uint32_t POFF = (uint32_t)(MAXR * sizeof(TA));   // (RP) the second array, in bytes
     int u = ua, o = 0;
-    auto next = [&](int& r0, int& cnt) {
+    auto next = [&](int& r0, int& cnt, int& un) {
         r0 = 0;
         cnt = 0;
+        un = 0;
         if (u >= ub) return;
         const int rr = __builtin_amdgcn_readlane(runv.x, u - ua), rn = __builtin_amdgcn_readlane(runv.y, u - ua);
+        if constexpr (VS) un = __builtin_amdgcn_readlane(runu, u - ua) + (o >> 1);   // (batches start at even rows)
         r0 = rr + o;
         cnt = min(G, rn - o);
         o += cnt;
@@ -758,7 +811,13 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
         }
     };
     // row pointers of a batch: lane j holds rp[r0 + min(j, cnt)] (rows past cnt are empty)
-    auto load_rp = [&](int r0, int cnt) -> int64_t {
+    auto load_rp = [&](int r0, int cnt, int un) -> int64_t {
+        if constexpr (VS) {
+            // the unit descriptors instead: lane j holds unit un + min(j, units) (the last: the batch's end)
+            const int nu = (cnt + 1) >> 1;
+            const __amdgpu_buffer_rsrc_t r = buf_rsrc(vs.desc + un, (nu + 1) * 8);
+            return __builtin_bit_cast(int64_t, __builtin_amdgcn_raw_buffer_load_b64(r, min(ln, nu) * 8, 0, 0));
+        }
         const __amdgpu_buffer_rsrc_t r = buf_rsrc(rp + r0, (cnt + 1) * 8);
         return __builtin_bit_cast(int64_t, __builtin_amdgcn_raw_buffer_load_b64(r, min(ln, cnt) * 8, 0, 0));
     };
@@ -773,9 +832,10 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
     };
     // lane l / GL's row of the batch at the group's first lane, past every range elsewhere
     auto row_off = [&]() { return (ln & (GL - 1)) == 0 ? (ln / GL) * ES : (1 << 30); };
-    auto issue = [&](RB& b, int r0, int cnt, int64_t rpv) {
+    auto issue = [&](RB& b, int r0, int cnt, int64_t rpv, int un) {
         b.r0 = r0;
         b.cnt = cnt;
+        (void)un;
         {   // (no xt / ev: an empty range, no memory access)
             const __amdgpu_buffer_rsrc_t rx = buf_rsrc(xt + r0, xt ? cnt * ES : 0);
             b.xv = buf_load<T>(rx, row_off());
@@ -785,6 +845,36 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
             } else {
                 b.evv = T(0);
             }
+        }
+        if constexpr (VS) {
+            // the batch's units are consecutive in both streams: one resource each, a unit is an SGPR
+            // offset into it; b.len[2u] = the first row's entries, b.off[2u] = whether the unit exists
+            const int nu = (cnt + 1) >> 1;
+            const uint32_t dlo = (uint32_t)rpv, dhi = (uint32_t)((uint64_t)rpv >> 32);
+            const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)dlo, 0);
+            const uint32_t pN = (uint32_t)__builtin_amdgcn_readlane((int)dlo, G / 2);
+            const __amdgpu_buffer_rsrc_t rv = buf_rsrc(val + 2 * (int64_t)p0, (int)((pN - p0) * 16u));
+            const __amdgpu_buffer_rsrc_t rl = buf_rsrc(lidx + 128 * (int64_t)un, nu * 256);
+#pragma unroll
+            for (int u = 0; u < G / 2; ++u) {
+                const bool live = u < nu;
+                const uint32_t pa = (uint32_t)__builtin_amdgcn_readlane((int)dlo, u);
+                const uint32_t pb = (uint32_t)__builtin_amdgcn_readlane((int)dlo, u + 1);
+                const uint32_t cw = (uint32_t)__builtin_amdgcn_readlane((int)dhi, u);
+                b.len[2 * u] = live ? (int)(cw & 0xffu) : 0;
+                b.len[2 * u + 1] = 0;
+                b.off[2 * u] = live ? 1 : 0;
+                const int c0h = live ? (int)((cw >> 8) & 0xffu) : 0;
+                const int np = live ? (int)(pb - pa) : 0;      // the unit's value pairs
+                const int t = ln - c0h;
+                const int vo = (uint32_t)t < (uint32_t)np ? t * 16 : (1 << 30);
+                const int lo = live ? ln * 4 : (1 << 30);
+                const double2 tv = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rv, vo, (int)((pa - p0) * 16u), HGM_RW_AUX));
+                b.v[u][0][0] = (T)tv.x;
+                b.v[u][0][EPL - 1] = (T)tv.y;
+                b.s[u][0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rl, lo, u * 256, HGM_RW_AUX);
+            }
+            return;
         }
         // (pairs) the batch's entries from its first row's first pair; inside a batch the row
         // pointers are 32-bit offsets from it
@@ -935,6 +1025,38 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
                 }
                 P[2 * u] = isA ? p : T(0);
                 P[2 * u + 1] = isA ? T(0) : p;
+            }
+        } else if constexpr (VS) {
+            const uint32_t dm = (uint32_t)(MAXR - 64 + ln) * (uint32_t)ES;
+#pragma unroll
+            for (int u = 0; u < G / 2; ++u) {
+                const int la = b.len[2 * u];
+                // (a unit that does not exist: every lane on its dummy, as the plan pads a unit's end)
+                const uint32_t s = b.off[2 * u] ? b.s[u][0] : (dm | (dm << 16) | 0xc007c007u);
+                T pa = T(0), pb = T(0);
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) {
+                    const bool inA = 2 * ln + e < la;
+                    const uint32_t sl = (e ? s >> 16 : s) & 0x3ff8u;
+                    // the code's table offset ((31 - code) * 8): bits 14-18 of the word, or bits 30-31 | 0-2
+                    const uint32_t c8 = (e ? __builtin_amdgcn_alignbit(s, s, 27) : s >> 11) & 0xf8u;
+                    const T v = b.v[u][0][e] + *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + VTAB * ES + c8);
+                    b.v[u][0][e] = v;
+                    const uint32_t ka = inA ? sl : dm, kk = inA ? dm : sl;
+                    const T qa = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + ka);
+                    const T qb = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + kk);
+                    if constexpr (HGM_FUSED_FMA) {
+                        pa = fma_t(v, qa, pa);
+                        pb = fma_t(v, qb, pb);
+                    } else {
+                        pa = pa + v * qa;
+                        pb = pb + v * qb;
+                    }
+                    k[u][0][e] = ka;
+                    kb[u][e] = kk;
+                }
+                P[2 * u] = pa;
+                P[2 * u + 1] = pb;
             }
         } else if constexpr (RP == 1 || RP >= 3) {
 #pragma unroll
@@ -1115,16 +1237,16 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
     // batch is processed as a no-op (zero-length ranges, dummy slots).  sched_barrier: the
     // scheduler would sink the next batch's loads into the processing.
     RB b[D];
-    int a[D], cn[D];
+    int a[D], cn[D], un[D];
     int64_t r[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-        next(a[i], cn[i]);
-        r[i] = load_rp(a[i], cn[i]);
+        next(a[i], cn[i], un[i]);
+        r[i] = load_rp(a[i], cn[i], un[i]);
     }
     stage();                                      // (the gathers' waits leave the row pointers in flight)
 #pragma unroll
-    for (int i = 0; i < D - 1; ++i) issue(b[i], a[i], cn[i], r[i]);
+    for (int i = 0; i < D - 1; ++i) issue(b[i], a[i], cn[i], r[i], un[i]);
     __syncthreads();                              // the staged q and the zeroed accumulators
     do {
 #pragma unroll
@@ -1132,9 +1254,9 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
             // the row pointers of batch i+D first: issuing batch i+D-1 then waits only for its
             // own row pointers (loaded before batch i+D-2's entries), not for the entries
             const int ti = (t + D - 1) % D;
-            next(a[t], cn[t]);
-            r[t] = load_rp(a[t], cn[t]);
-            issue(b[ti], a[ti], cn[ti], r[ti]);
+            next(a[t], cn[t], un[t]);
+            r[t] = load_rp(a[t], cn[t], un[t]);
+            issue(b[ti], a[ti], cn[ti], r[ti], un[ti]);
             __builtin_amdgcn_sched_barrier(0);
             process(b[t]);
             __builtin_amdgcn_sched_barrier(0);
@@ -1578,6 +1700,289 @@ static void plan_bands(FusedPlan* P, const std::vector<int32_t>& ray_tab, const 
     P->band_run = upload(run);
 }
 
+// ------------------------------------------------------------------------------------------
+// Compact value stream (HGM_OPT_FUSED_VSTREAM, k_fused_rw RP 5): built on the device from B's values
+// and the plan's lidx, once per plan, after either build of the ray sets (so a host-built and a
+// device-built plan hold the same bytes).  Every step is order-free or in a fixed order: the
+// dictionary from a fixed-stride sample sorted on the host, integer counts, ranks by wave ballots
+// in CSR order.
+// ------------------------------------------------------------------------------------------
+namespace {
+constexpr int VS_CODES = 31;
+constexpr int64_t VS_SAMPLE = int64_t(1) << 20;
+// Take the compact streams when the pass's entry bytes (values, slots, row pointers or descriptors)
+// shrink by at least this share.  The decode costs 3.3 % of the pass at C4 (empty dictionary, every
+// value stored: 2,089 us against 2,023 us plain), the compact streams must save twice that, 6.5 % of the
+// pass's bytes, and the entry streams are 86 % of those (10.17 of 11.81 GB): 7.6 %, rounded up.  With
+// Siddon row lengths that is a coverage of about 12 % (C4: 29 % coded, entry bytes x 0.788).
+// DESIGN.md §3.5.
+constexpr double VS_MIN_SAVING = 0.08;
+
+struct VsDict {
+    uint64_t bits[32];            // ascending; code = index + 1
+    int n;
+};
+
+__global__ void k_vs_sample(const double* __restrict__ val, int64_t stride, int64_t ns, uint64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ns) out[i] = (uint64_t)__double_as_longlong(val[i * stride]);
+}
+
+// code of a value (0: none), by binary search in the sorted dictionary
+__device__ __forceinline__ int vs_code(const VsDict& d, uint64_t x) {
+    int lo = 0, hi = d.n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (d.bits[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < d.n && d.bits[lo] == x) ? lo + 1 : 0;
+}
+
+// One wave per unit (unit_row: first row | single-row flag << 31): the unit's entries are CSR entries
+// e0 .. e2, lane l taking e0 + l and e0 + l + 64.  pos[r]: the entry's position in the reordered unit.
+struct VsUnit {
+    int64_t e0;
+    int n, nA;                    // entries, first row's entries
+    int nCA, nEA, nEB, nCB;
+    int code[2], pos[2];
+    bool valid[2];
+    uint64_t bits[2];
+};
+__device__ __forceinline__ VsUnit vs_unit(const VsDict& d, uint32_t ur, const int64_t* __restrict__ rp,
+                                          const double* __restrict__ val, bool live) {
+    VsUnit U;
+    const int row = (int)(ur & 0x7fffffffu);
+    const bool single = (ur >> 31) != 0;
+    const int ln = threadIdx.x & 63;
+    const int64_t e0 = live ? rp[row] : 0, e1 = live ? rp[row + 1] : 0, e2 = live ? (single ? e1 : rp[row + 2]) : 0;
+    U.e0 = e0;
+    U.n = (int)(e2 - e0);
+    U.nA = (int)(e1 - e0);
+    uint64_t m[4][2];
+    const uint64_t lt = ((uint64_t)1 << ln) - 1;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = ln + 64 * r;
+        U.valid[r] = i < U.n;
+        U.bits[r] = U.valid[r] ? (uint64_t)__double_as_longlong(val[e0 + i]) : 0;
+        U.code[r] = U.valid[r] ? vs_code(d, U.bits[r]) : 0;
+        const bool isA = i < U.nA, cd = U.code[r] != 0;
+        m[0][r] = __ballot(U.valid[r] && isA && cd);
+        m[1][r] = __ballot(U.valid[r] && isA && !cd);
+        m[2][r] = __ballot(U.valid[r] && !isA && !cd);
+        m[3][r] = __ballot(U.valid[r] && !isA && cd);
+    }
+    U.nCA = __popcll(m[0][0]) + __popcll(m[0][1]);
+    U.nEA = __popcll(m[1][0]) + __popcll(m[1][1]);
+    U.nEB = __popcll(m[2][0]) + __popcll(m[2][1]);
+    U.nCB = __popcll(m[3][0]) + __popcll(m[3][1]);
+    const int base[4] = {0, U.nCA, U.nCA + U.nEA, U.nCA + U.nEA + U.nEB};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = ln + 64 * r;
+        const bool isA = i < U.nA, cd = U.code[r] != 0;
+        const int cls = isA ? (cd ? 0 : 1) : (cd ? 3 : 2);
+        int rank = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (cls == q) rank = __popcll(m[q][r] & lt) + (r ? __popcll(m[q][0]) : 0);
+        U.pos[r] = base[cls] + rank;
+    }
+    return U;
+}
+
+// per unit: its value pairs and descriptor word (bits 16-23: the unit's coded entries, summed and
+// cleared by the host: one atomic per unit on one counter cost 0.1 s at C4); *nan += NaN values
+__global__ __launch_bounds__(256) void k_vs_count(VsDict d, int64_t nunit, const uint32_t* __restrict__ unit_row,
+                                                  const int64_t* __restrict__ rp, const double* __restrict__ val,
+                                                  uint2* __restrict__ desc, unsigned long long* __restrict__ nan) {
+    const int64_t un = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = un < nunit;
+    const VsUnit U = vs_unit(d, live ? unit_row[un] : 0u, rp, val, live);
+    int isnan_ = 0;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+        isnan_ += (U.valid[r] && (U.bits[r] & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) ? 1 : 0;
+    const int nans = __popcll(__ballot(isnan_ & 1)) + __popcll(__ballot(isnan_ & 2)) * 2;
+    if (live && (threadIdx.x & 63) == 0) {
+        const int nE = U.nEA + U.nEB;             // (no escapes: no pair, whatever the parity of nCA)
+        const int np = nE ? ((U.nCA & 1) + nE + 1) >> 1 : 0;
+        desc[un] = make_uint2((uint32_t)np, (uint32_t)U.nA | ((uint32_t)(U.nCA >> 1) << 8) |
+                                                ((uint32_t)(U.nCA + U.nCB) << 16));
+        if (nans) atomicAdd(nan, (unsigned long long)nans);
+    }
+}
+
+// the unit's slot words and escape values (vals is zeroed beforehand: the positions that hold no
+// escape); desc.x now holds the unit's first value pair
+__global__ __launch_bounds__(256) void k_vs_fill(VsDict d, int64_t nunit, const uint32_t* __restrict__ unit_row,
+                                                 const int64_t* __restrict__ rp, const double* __restrict__ val,
+                                                 const uint16_t* __restrict__ lidx, const uint2* __restrict__ desc,
+                                                 int maxr, uint32_t* __restrict__ slots, double* __restrict__ vals) {
+    __shared__ uint16_t s16[4][128];
+    __shared__ uint8_t c8[4][128];
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    const int64_t un = (int64_t)blockIdx.x * 4 + wv;
+    const bool live = un < nunit;
+    const VsUnit U = vs_unit(d, live ? unit_row[un] : 0u, rp, val, live);
+    const uint16_t dm = (uint16_t)((maxr - 64 + ln) * 8);
+    s16[wv][2 * ln] = dm;
+    s16[wv][2 * ln + 1] = dm;
+    c8[wv][2 * ln] = 0;
+    c8[wv][2 * ln + 1] = 0;
+    __syncthreads();
+    const int64_t v0 = live ? 2 * (int64_t)desc[un].x - (U.nCA & ~1) : 0;   // value index of position 0
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (U.valid[r]) {
+            s16[wv][U.pos[r]] = lidx[U.e0 + ln + 64 * r];
+            c8[wv][U.pos[r]] = (uint8_t)U.code[r];
+            if (U.code[r] == 0) vals[v0 + U.pos[r]] = __longlong_as_double((long long)U.bits[r]);
+        }
+    }
+    __syncthreads();
+    if (live) {
+        // (the fields hold 31 - code: the table grows down from the dummies)
+        const uint32_t a = s16[wv][2 * ln], b = s16[wv][2 * ln + 1], ca = 31u - c8[wv][2 * ln], cb = 31u - c8[wv][2 * ln + 1];
+        slots[un * 64 + ln] = a | (b << 16) | (ca << 14) | ((cb & 3u) << 30) | (cb >> 2);
+    }
+}
+}  // namespace
+
+// Adds the compact streams to a finished fp64 row-pair-4 plan when the options, the plan's shape and
+// the operator's values allow it (otherwise the plan stays plain: today's streams, today's bits).
+static void fused_plan_vstream(hgm_ctx* c, const hgm_mat* B, FusedPlan* P, const std::vector<int2>& runs, int worst) {
+    const int mode = c->num.fused_vstream;
+    const auto tv0 = std::chrono::steady_clock::now();
+    P->nnz = B->nnz;
+    if (!mode || P->kind != 1 || P->elem != 8 || P->rowpair != 4 || P->waves != 4 || P->group != 8 || P->depth != 2 ||
+        !P->pairs || P->maxr > 2048 || worst > P->maxr - 65 || c->num.fused_dbg || B->nnz <= 0)
+        return;
+    const int room = std::min(VS_CODES, P->maxr - 65 - worst);   // codes the fullest region leaves slots for
+    const int64_t nnz = B->nnz, nrun = (int64_t)runs.size();
+    std::vector<int32_t> run_unit(std::max<int64_t>(nrun, 1), 0);
+    int64_t nunit = 0;
+    for (int64_t i = 0; i < nrun; ++i) {
+        run_unit[i] = (int32_t)nunit;
+        nunit += (runs[i].y + 1) / 2;
+    }
+    if (nunit <= 0 || nunit >= (int64_t(1) << 31) - 4) return;
+    std::vector<uint32_t> unit_row(nunit);
+    parallel_for(nrun, [&](int64_t i) {
+        for (int k = 0; 2 * k < runs[i].y; ++k)
+            unit_row[run_unit[i] + k] = (uint32_t)(runs[i].x + 2 * k) | (2 * k + 1 == runs[i].y ? 0x80000000u : 0u);
+    });
+    // the dictionary: the sample's most frequent patterns (seen at least twice; ties by bit pattern), finite,
+    // normal and non-zero (0.0 + t must give t's bits)
+    VsDict d{};
+    uint64_t* samp_d = nullptr;
+    uint32_t* unit_row_d = nullptr;
+    unsigned long long* tot_d = nullptr;
+    auto drop = [&](auto*& p) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    };
+    auto cleanup = [&]() {
+        drop(samp_d);
+        drop(unit_row_d);
+        drop(tot_d);
+    };
+    auto give_up = [&]() {       // the plan stays plain
+        cleanup();
+        drop(P->vs_desc);
+        drop(P->vs_run_unit);
+        drop(P->vs_table);
+        drop(P->vs_slots);
+        drop(P->vs_vals);
+        P->vs_on = false;
+        P->vs_pairs = 0;
+        (void)hipGetLastError();
+    };
+    try {
+        if (mode != 2) {
+            const int64_t ns = std::min(nnz, VS_SAMPLE), stride = nnz / ns;
+            if (hipMalloc(&samp_d, sizeof(uint64_t) * ns) != hipSuccess) return give_up();
+            hipLaunchKernelGGL(k_vs_sample, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream,
+                               (const double*)B->val, stride, ns, samp_d);
+            HGM_HIP(hipGetLastError());
+            std::vector<uint64_t> s(ns);
+            HGM_HIP(hipMemcpyAsync(s.data(), samp_d, sizeof(uint64_t) * ns, hipMemcpyDeviceToHost, c->stream));
+            HGM_HIP(hipStreamSynchronize(c->stream));
+            std::sort(s.begin(), s.end());
+            std::vector<std::pair<int64_t, uint64_t>> cand;   // (-count, bits)
+            for (int64_t i = 0; i < ns;) {
+                int64_t j = i;
+                while (j < ns && s[j] == s[i]) ++j;
+                const uint64_t ex = (s[i] >> 52) & 0x7ffu;
+                if (j - i >= 2 && ex != 0 && ex != 0x7ffu) cand.emplace_back(-(j - i), s[i]);
+                i = j;
+            }
+            std::sort(cand.begin(), cand.end());
+            d.n = (int)std::min<size_t>(cand.size(), (size_t)room);
+            for (int i = 0; i < d.n; ++i) d.bits[i] = cand[i].second;
+            std::sort(d.bits, d.bits + d.n);
+        }
+        if (mode == 1 && d.n == 0) return give_up();
+        P->vs_desc = upload(std::vector<uint2>(nunit + 1, make_uint2(0, 0)));
+        P->vs_run_unit = upload(run_unit);
+        unit_row_d = upload(unit_row);
+        tot_d = upload(std::vector<unsigned long long>(2, 0ull));
+        const unsigned grid = (unsigned)((nunit + 3) / 4);
+        hipLaunchKernelGGL(k_vs_count, dim3(grid), dim3(256), 0, c->stream, d, nunit, (const uint32_t*)unit_row_d,
+                           (const int64_t*)B->rp, (const double*)B->val, P->vs_desc, tot_d + 1);
+        HGM_HIP(hipGetLastError());
+        std::vector<uint2> desc(nunit + 1);
+        unsigned long long tot[2] = {0, 0};
+        HGM_HIP(hipMemcpyAsync(desc.data(), P->vs_desc, sizeof(uint2) * (nunit + 1), hipMemcpyDeviceToHost, c->stream));
+        HGM_HIP(hipMemcpyAsync(tot, tot_d, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+        HGM_HIP(hipStreamSynchronize(c->stream));
+        int64_t pairs = 0, coded = 0;
+        for (int64_t i = 0; i <= nunit; ++i) {     // value pairs per unit -> first pair (exclusive scan)
+            const int64_t np = i < nunit ? desc[i].x : 0;
+            desc[i].x = (uint32_t)pairs;
+            pairs += np;
+            coded += desc[i].y >> 16;
+            desc[i].y &= 0xffffu;
+        }
+        tot[0] = (unsigned long long)coded;
+        // entry bytes of the pass: plain 8 (value) + 2 (slot) per entry + 8 per row; compact 16 per
+        // value pair + 256 (slots) + 8 (descriptor) per unit
+        const double plain = 10.0 * (double)nnz + 8.0 * (double)B->rows;
+        const double compact = 16.0 * (double)pairs + 264.0 * (double)nunit;
+        const bool worth = compact <= (1.0 - VS_MIN_SAVING) * plain;
+        P->vs_coded = (int64_t)tot[0];
+        if (tot[1] != 0 || pairs >= (int64_t(1) << 32) || (mode == 1 && !worth)) return give_up();
+        HGM_HIP(hipMemcpyAsync(P->vs_desc, desc.data(), sizeof(uint2) * (nunit + 1), hipMemcpyHostToDevice, c->stream));
+        std::vector<double> table(32, 0.0);
+        table[31] = -0.0;
+        for (int i = 0; i < d.n; ++i) std::memcpy(&table[31 - (i + 1)], &d.bits[i], 8);
+        P->vs_table = upload(table);
+        if (hipMalloc(&P->vs_slots, sizeof(uint32_t) * 64 * (size_t)nunit) != hipSuccess ||
+            hipMalloc(&P->vs_vals, 16 * (size_t)std::max<int64_t>(pairs, 1)) != hipSuccess)
+            return give_up();                      // (no room for the second copy: the plain plan)
+        HGM_HIP(hipMemsetAsync(P->vs_vals, 0, 16 * (size_t)std::max<int64_t>(pairs, 1), c->stream));
+        hipLaunchKernelGGL(k_vs_fill, dim3(grid), dim3(256), 0, c->stream, d, nunit, (const uint32_t*)unit_row_d,
+                           (const int64_t*)B->rp, (const double*)B->val, (const uint16_t*)P->lidx,
+                           (const uint2*)P->vs_desc, P->maxr, P->vs_slots, P->vs_vals);
+        HGM_HIP(hipGetLastError());
+        HGM_HIP(hipStreamSynchronize(c->stream));
+        P->nunit = nunit;
+        P->vs_pairs = pairs;
+        P->vs_on = true;
+        cleanup();
+        if (std::getenv("HGM_FUSED_VERBOSE"))
+            std::fprintf(stderr, "[fused rw plan, value stream] %d codes cover %.4f of %lld entries; %lld units, values %lld B "
+                         "(%.3f B/entry), slots %lld B; entry bytes %.4f of the plain streams'; %.3f s\n",
+                         d.n, (double)P->vs_coded / (double)nnz, (long long)nnz, (long long)nunit, (long long)(16 * pairs),
+                         16.0 * (double)pairs / (double)nnz, (long long)(256 * nunit), compact / plain,
+                         std::chrono::duration<double>(std::chrono::steady_clock::now() - tv0).count());
+    } catch (...) {
+        give_up();
+        throw;
+    }
+}
+
 // The one refusal a smaller region can cure (fused_ab_plan retries it with half the side); every
 // other refusal of a plan (option shapes without a kernel, index ranges) goes straight to the
 // two-pass path.
@@ -1595,6 +2000,7 @@ static FusedPlan* fused_plan_dev_finish(hgm_ctx* c, const hgm_mat* B, int R, int
     const int nwords = (int)((m + 31) / 32);
     FusedPlan* P = new FusedPlan;
     int32_t* cnt_d = nullptr;
+    int worst_rays = 0;
     try {
         P->kind = 1;
         P->elem = es;
@@ -1620,6 +2026,7 @@ static FusedPlan* fused_plan_dev_finish(hgm_ctx* c, const hgm_mat* B, int R, int
         HGM_HIP(hipStreamSynchronize(c->stream));
         int worst = 0;
         for (int32_t v : cnt) worst = std::max(worst, (int)v);
+        worst_rays = worst;
         int maxr = 0;
 #define HGM_RW_PICK(WV, MRV) \
     if (W == WV && worst <= MRV - 64 && (maxr == 0 || MRV < maxr)) maxr = MRV;
@@ -1674,6 +2081,14 @@ static FusedPlan* fused_plan_dev_finish(hgm_ctx* c, const hgm_mat* B, int R, int
         fused_plan_free(P);
         throw Error{HGM_E_ARG, "fused A*(B*q): no row-wave kernel for this plan's shape and the options"};
     }
+    P->nwrun = (int64_t)runs.size();
+    try {
+        fused_plan_vstream(c, B, P, runs, worst_rays);
+    } catch (...) {
+        fused_plan_free(P);
+        throw;
+    }
+    P->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (std::getenv("HGM_FUSED_VERBOSE"))
         std::fprintf(stderr, "[fused rw plan, device] region %d waves %d: %lld regions, %lld slots, max rays %d (LDS slots %d), %.3f s\n",
                      R, W, (long long)nreg, (long long)P->nslot, 0, P->maxr, P->build_s);
@@ -1864,6 +2279,14 @@ FusedPlan* fused_plan_build_rw(hgm_ctx* c, const hgm_mat* B, int R, int W, int G
         fused_plan_free(P);
         throw Error{HGM_E_ARG, "fused A*(B*q): no row-wave kernel for this plan's shape and the options"};
     }
+    P->nwrun = (int64_t)runs.size();
+    try {
+        fused_plan_vstream(c, B, P, runs, worst.load());
+    } catch (...) {
+        fused_plan_free(P);
+        throw;
+    }
+    P->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (std::getenv("HGM_FUSED_VERBOSE"))
         std::fprintf(stderr, "[fused rw plan] region %d waves %d group %d: %lld regions, %lld slots, max rays %d (LDS slots %d), longest row %lld, %d runs, %.2f s\n",
                      R, W, G, (long long)nreg, (long long)nslot, worst.load(), maxr, (long long)maxlen, wrun.back(), P->build_s);
@@ -1888,7 +2311,7 @@ static int64_t fused_key(const Numerics& nu) {
     if (!rw) return ((int64_t)nu.fused_region << 1);
     return 1 | ((int64_t)nu.fused_wregion << 1) | ((int64_t)nu.fused_waves << 10) | ((int64_t)nu.fused_group << 13) |
            ((int64_t)nu.fused_depth << 17) | ((int64_t)nu.fused_pairs << 20) | ((int64_t)nu.fused_acc32 << 21) |
-           ((int64_t)nu.fused_plan_dev << 23) | ((int64_t)nu.fused_rowpair << 24);
+           ((int64_t)nu.fused_plan_dev << 23) | ((int64_t)nu.fused_rowpair << 24) | ((int64_t)nu.fused_vstream << 27);
 }
 
 // The plan of B, built on first use (a failure to plan leaves the two-pass path in place).
@@ -1956,7 +2379,19 @@ static bool fused_rw_launch(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P, co
                    dim3(64 * WV), (const int64_t*)P->reg_base, (const int32_t*)P->ray_tab, (const int32_t*)P->wrun, \
                    (const int2*)P->runs, (const int64_t*)B->rp, (const T*)B->val, (const uint16_t*)P->lidx, fa.q,  \
                    fa.zraw, (typename AccT<T, AMV>::t*)P->part, side ? fa.xt : nullptr,                            \
-                   side ? (T*)P->zx_part : nullptr, fa.ev, fa.easq, fa.zout, fa.side_sq ? 1 : 0, fa.pn);           \
+                   side ? (T*)P->zx_part : nullptr, fa.ev, fa.easq, fa.zout, fa.side_sq ? 1 : 0, fa.pn, VStream{}); \
+        return true;                                                                                                  \
+    }
+    // the compact value stream (RP 5): the plan's streams in place of B's values, lidx and row pointers
+#define HGM_RWLV(MRV)                                                                                                \
+    {                                                                                                                 \
+        if (!dry)                                                                                                     \
+            launch(c, false, k_fused_rw<T, GK, 0, 4, MRV, 8, 1, 2, true, 0, 5>, dim3((unsigned)P->nreg), dim3(256), \
+                   (const int64_t*)P->reg_base, (const int32_t*)P->ray_tab, (const int32_t*)P->wrun,                \
+                   (const int2*)P->runs, (const int64_t*)nullptr, (const T*)P->vs_vals,                             \
+                   (const uint16_t*)P->vs_slots, fa.q, fa.zraw, (T*)P->part, side ? fa.xt : nullptr,                \
+                   side ? (T*)P->zx_part : nullptr, fa.ev, fa.easq, fa.zout, fa.side_sq ? 1 : 0, fa.pn,             \
+                   VStream{P->vs_desc, P->vs_run_unit, P->vs_table});                                                \
         return true;                                                                                                  \
     }
     if (P->rowpair) {
@@ -1974,6 +2409,14 @@ static bool fused_rw_launch(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P, co
         }
         // mode 4 (the default) for every four-wave shape; modes 1-3 (measured variants)
         // for the C4/C5 shape only
+        if constexpr (sizeof(T) == 8 && !GK) {
+            if (P->rowpair == 4 && P->vs_on) {
+                if (MR == 1088) HGM_RWLV(1088)
+                if (MR == 1344) HGM_RWLV(1344)
+                if (MR == 1536) HGM_RWLV(1536)
+                if (MR == 2048) HGM_RWLV(2048)
+            }
+        }
         if (P->rowpair == 4) {
             if (MR == 1088) HGM_RWLR(AMP, 4, 1088, 8, 1, 2, true, 0, 4)
             if (MR == 1344) HGM_RWLR(AMP, 4, 1344, 8, 1, 2, true, 0, 4)
@@ -2053,6 +2496,7 @@ static bool fused_rw_launch(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P, co
     }
 #undef HGM_RWL
 #undef HGM_RWLR
+#undef HGM_RWLV
     if (dry) return false;
     throw Error{HGM_E_ARG, "fused A*(B*q): no row-wave kernel for this plan and options"};
 }
@@ -2217,6 +2661,17 @@ uint64_t fused_plan_checksum(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P) {
         mix(P->band_ptr, sizeof(int32_t) * (P->nband + 1));
         mix(P->band_run, sizeof(int4) * P->nrun);
     }
+    if (P->vs_on) {                               // (large arrays in pieces: bounded host memory)
+        auto mix_big = [&](const void* dev, size_t bytes) {
+            const size_t step = size_t(256) << 20;
+            for (size_t o = 0; o < bytes; o += step) mix((const char*)dev + o, std::min(step, bytes - o));
+        };
+        mix(P->vs_desc, sizeof(uint2) * (P->nunit + 1));
+        mix(P->vs_run_unit, sizeof(int32_t) * nrun);
+        mix(P->vs_table, sizeof(double) * 32);
+        mix_big(P->vs_slots, sizeof(uint32_t) * 64 * (size_t)P->nunit);
+        mix_big(P->vs_vals, 16 * (size_t)P->vs_pairs);
+    }
     const int64_t meta[6] = {P->elem, P->region, P->waves, P->maxr, P->maxlen, P->nslot};
     for (int64_t v : meta)
         for (int k = 0; k < 8; ++k) h = (h ^ (unsigned char)(v >> (8 * k))) * 1099511628211ull;
@@ -2226,4 +2681,19 @@ uint64_t fused_plan_checksum(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P) {
 double fused_plan_build_seconds(const FusedPlan* P) { return P->build_s; }
 int64_t fused_plan_slots(const FusedPlan* P) { return P->nslot; }
 bool fused_plan_device_built(const FusedPlan* P) { return P->dev_built; }
+void fused_plan_vstream_info(const FusedPlan* P, int* active, double* coverage, int64_t* value_bytes,
+                             int64_t* plan_bytes) {
+    if (active) *active = P->vs_on ? 1 : 0;
+    if (coverage) *coverage = P->vs_on && P->nnz > 0 ? (double)P->vs_coded / (double)P->nnz : 0.0;
+    if (value_bytes) *value_bytes = P->vs_on ? 16 * P->vs_pairs : 0;
+    if (plan_bytes) {
+        int64_t b = 0;
+        if (P->kind == 1) {
+            b = 4 * (P->nreg * P->waves + 1) + 8 * P->nwrun + 8 * (P->nreg + 1) + 4 * P->nslot + 2 * (P->nnz + 256) +
+                8 * (P->m + 1) + 4 * P->nslot + 4 * (P->nband + 1) + 16 * P->nrun + 8 * P->nslot + 8 * P->nreg;
+            if (P->vs_on) b += 8 * (P->nunit + 1) + 4 * P->nwrun + 256 + 256 * P->nunit + 16 * P->vs_pairs;
+        }
+        *plan_bytes = b;
+    }
+}
 }  // namespace hgm

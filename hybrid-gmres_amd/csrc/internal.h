@@ -101,6 +101,8 @@ struct Numerics {
     int fused_acc32 = 1;            // ... fp32 row-wave pass: 0 ds_add_f32, 1 read-add-write, 2 fp64 accumulators
     bool fused_plan_dev = true;     // ... row-wave plan's ray sets built on the device (false: the host build)
     int fused_rowpair = 4;          // ... row-wave pass: units of two consecutive rows per chunk (k_fused_rw RP 1-4)
+    int fused_vstream = 1;          // ... row-wave pass, fp64 row-pair mode 4: compact value stream with in-slot codes
+                                    //     (0 plain, 1 when it saves enough bytes, 2 / 3 measurement forms; fused.hip)
     int fused_reduce = 0;           // ... row-wave partial reduction: 0 by ray (rs_slot), 1 by ray band (runs;
                                     //     bitwise equal, measured 2-4% slower pass at C4, profiles/r4_c4_reduce_band_ab.jsonl)
     bool lsqr_res_img = true;       // one-pass LSQR: final residual from the A*x image (no SpMV)
@@ -630,6 +632,10 @@ uint64_t fused_plan_checksum(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P);
 double fused_plan_build_seconds(const FusedPlan* P);
 int64_t fused_plan_slots(const FusedPlan* P);
 bool fused_plan_device_built(const FusedPlan* P);
+// the plan's compact value stream (HGM_OPT_FUSED_VSTREAM): whether the pass reads it, the share of
+// B's entries that carry a dictionary code, the bytes of the compact values, the plan's device bytes
+void fused_plan_vstream_info(const FusedPlan* P, int* active, double* coverage, int64_t* value_bytes,
+                             int64_t* plan_bytes);
 
 // Solver entry check: HGM_OPT_FUSED_DBG skips phases of the one-pass kernel (timing experiments of
 // hgm_spmv_ab only, scripts/fused_micro.py): a solve would return wrong results, so it is refused.

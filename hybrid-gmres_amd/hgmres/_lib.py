@@ -28,6 +28,13 @@ OPTIONS = {"parity": 1, "mgs_form": 2, "mgs_single": 3, "gram_err": 4, "gram_err
            "fused_depth": 28, "fused_pairs": 29, "fused_acc32": 30, "fused_plan_dev": 31, "fused_reduce": 32,
            "host_spin_us": 33, "fused_rowpair": 34,
            "lsqr_res_img": 35, "lsmr_fuse_nmon": 36}
+# options from 37 on (OPTIONS is the table of options 1-36; Context.set_option / get_option take both)
+OPTIONS_37 = {"fused_vstream": 37}
+
+
+def option_id(name):
+    return OPTIONS[name] if name in OPTIONS else OPTIONS_37[name]
+
 HGM_MGS, HGM_CGS2 = 0, 1
 HGM_SIDE_AB, HGM_SIDE_BA = 0, 1
 HGM_DEVICE_PTRS = 1
@@ -68,6 +75,8 @@ _SIGS = {
     "hgm_mem_info": (c_int, [c_void_p, P(c_int64), P(c_int64)]),
     "hgm_ctx_solve_path": (c_int, [c_void_p, c_int, P(c_int), c_int, P(c_int)]),
     "hgm_mat_create_csr": (c_int, [c_void_p, c_int64, c_int64, c_int64, ip64, ip32, dp, c_int, P(c_void_p)]),
+    "hgm_mat_create_csr_tiled": (c_int, [c_void_p, c_int64, c_int64, c_int64, ip64, ip32, dp, c_int, c_int, c_int, c_int,
+                                         P(c_void_p)]),
     "hgm_mat_create_csc": (c_int, [c_void_p, c_int64, c_int64, c_int64, ip64, ip64, dp, c_int, P(c_void_p)]),
     "hgm_mat_transpose": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
     "hgm_mat_create_siddon": (c_int, [c_void_p, c_int, c_int, c_double, c_int, P(c_void_p)]),
@@ -89,6 +98,7 @@ _SIGS = {
     "hgm_proj_norms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp, dp]),
     "hgm_proj_norms_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp]),
     "hgm_fused_plan_info": (c_int, [c_void_p, c_void_p, c_void_p, dp, P(C.c_uint64), ip64, P(c_int)]),
+    "hgm_fused_vstream_info": (c_int, [c_void_p, c_void_p, c_void_p, P(c_int), dp, ip64, ip64]),
     "hgm_dev_alloc": (c_int, [c_void_p, c_int64, P(c_void_p)]),
     "hgm_dev_free": (c_int, [c_void_p, c_void_p]),
     "hgm_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),

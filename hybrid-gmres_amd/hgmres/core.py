@@ -115,15 +115,15 @@ class Context:
         return out
 
     def set_option(self, name, value):
-        """Per-context numerics option (``hgm_ctx_set_option``; names in ``_lib.OPTIONS``),
+        """Per-context numerics option (``hgm_ctx_set_option``; names in ``_lib.OPTIONS`` and ``_lib.OPTIONS_37``),
         e.g. ``ctx.set_option("parity", 1)``.  Returns the previous value."""
         prev = self.get_option(name)
-        _check(L.load().hgm_ctx_set_option(self._h, L.OPTIONS[name], float(value)), self)
+        _check(L.load().hgm_ctx_set_option(self._h, L.option_id(name), float(value)), self)
         return prev
 
     def get_option(self, name):
         v = C.c_double()
-        _check(L.load().hgm_ctx_get_option(self._h, L.OPTIONS[name], C.byref(v)), self)
+        _check(L.load().hgm_ctx_get_option(self._h, L.option_id(name), C.byref(v)), self)
         return v.value
 
     def options(self, **kw):
@@ -250,6 +250,25 @@ class SparseOperator:
                                            rp.ctypes.data_as(L.ip64), ci.ctypes.data_as(L.ip32),
                                            _dp(va), dtype, C.byref(h)), ctx)
         return cls(ctx, h, M.shape, int(M.nnz), dtype)
+
+    @classmethod
+    def from_scipy_tiled(cls, M, N, tile, super_block=0, ctx: Context | None = None, dtype=L.HGM_F64):
+        """A ray-major operator from a scipy matrix whose columns are the pixels of an ``N x N`` image
+        in REFERENCE order, stored with the tiled pixel order ``(tile, super_block)`` (as
+        :meth:`siddon` stores its own): prescribed values over a tiled grid."""
+        ctx = ctx or default_context()
+        M = sp.csr_matrix(M)
+        pos = stored_pixel_index(N, tile, super_block)
+        Ms = sp.csr_matrix((M.data.copy(), pos[M.indices], M.indptr.copy()), shape=M.shape)   # (sorted in place below)
+        Ms.sort_indices()
+        rp = np.ascontiguousarray(Ms.indptr, dtype=np.int64)
+        ci = np.ascontiguousarray(Ms.indices, dtype=np.int32)
+        va = np.ascontiguousarray(Ms.data, dtype=np.float64)
+        h = C.c_void_p()
+        _check(L.load().hgm_mat_create_csr_tiled(ctx.handle, Ms.shape[0], Ms.shape[1], Ms.nnz,
+                                                 rp.ctypes.data_as(L.ip64), ci.ctypes.data_as(L.ip32), _dp(va),
+                                                 dtype, int(N), int(tile), int(super_block), C.byref(h)), ctx)
+        return cls._wrap(ctx, h)
 
     @classmethod
     def from_csc(cls, M, ctx: Context | None = None, dtype=L.HGM_F64):
@@ -474,12 +493,18 @@ def spmm(A: "SparseOperator", X):
 def fused_plan_info(A: "SparseOperator", B: "SparseOperator"):
     """The one-pass plan of (A, B) under the context's options (built if needed): dict with the
     build seconds, a checksum over every plan array, the partial slots and whether the device built
-    the ray sets (``hgm_fused_plan_info``)."""
+    the ray sets (``hgm_fused_plan_info``), and the compact value stream (``hgm_fused_vstream_info``):
+    whether the pass reads it, the share of coded entries, its value bytes and the plan's device bytes."""
     ctx = A.ctx
     bs, ck, ns, dv = C.c_double(), C.c_uint64(), C.c_int64(), C.c_int()
     _check(L.load().hgm_fused_plan_info(ctx.handle, A._h, B._h, C.byref(bs), C.byref(ck), C.byref(ns), C.byref(dv)),
            ctx)
-    return {"build_s": bs.value, "checksum": ck.value, "nslot": ns.value, "device_built": bool(dv.value)}
+    va, cov, vb, pb = C.c_int(), C.c_double(), C.c_int64(), C.c_int64()
+    _check(L.load().hgm_fused_vstream_info(ctx.handle, A._h, B._h, C.byref(va), C.byref(cov), C.byref(vb),
+                                           C.byref(pb)), ctx)
+    return {"build_s": bs.value, "checksum": ck.value, "nslot": ns.value, "device_built": bool(dv.value),
+            "vstream": bool(va.value), "vstream_coverage": cov.value, "vstream_value_bytes": vb.value,
+            "plan_bytes": pb.value}
 
 
 def as_operator(M, ctx=None, dtype=L.HGM_F64) -> SparseOperator:

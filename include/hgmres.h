@@ -178,7 +178,15 @@ enum hgm_ctx_option {
                                       pass's A*v_hat / alpha) instead of one more SpMV [1] */,
     HGM_OPT_LSMR_FUSE_NMON = 36    /* one-pass lsmr_solver with x_true: the n-space step (:40, :61-67, :72)
                                       and the n-space monitor (:71's A'r image) in one launch [1] (the
-                                      same bits as two) */
+                                      same bits as two) */,
+    HGM_OPT_FUSED_VSTREAM = 37     /* ... row-wave pass, fp64 row-pair mode 4 with at most 2,048 LDS slots: a
+                                      plan-owned compact value stream (the up to 31 most frequent value bit
+                                      patterns become codes in the free bits of the entries' slot words, only
+                                      the other values are stored; decoded bit for bit) [1]: 0 the plain
+                                      streams, 1 compact when the plan's entry bytes shrink enough (DESIGN.md
+                                      §3.5; otherwise the plain plan, bit-identical to 0), 3 compact whenever
+                                      the plan's shape allows it, 2 as 3 with an empty dictionary (every value
+                                      stored: the decode overhead measurement) */
 };
 
 /* Host all-reduce hook (sum, in place, host memory) used instead of RCCL for
@@ -236,6 +244,13 @@ HGM_API int hgm_mat_create_csr(hgm_ctx* ctx, int64_t rows, int64_t cols, int64_t
 /* MATLAB sparse hand-over: CSC of an rows x cols matrix (jc: cols+1, ir: nnz,
  * pr: nnz, 64-bit mwIndex).  The device CSR (row-major) is built by a
  * deterministic device transpose. */
+/* As hgm_mat_create_csr for a ray-major operator whose COLUMNS are the pixels of an N x N image
+ * already in the stored tiled order (tile, super_block) of hgm_mat_create_siddon_ordered (column
+ * index = the pixel's stored position): an operator with prescribed values over a tiled pixel
+ * grid, e.g. for the one-pass A*(B*q) with its device transpose. */
+HGM_API int hgm_mat_create_csr_tiled(hgm_ctx* ctx, int64_t rows, int64_t cols, int64_t nnz, const int64_t* row_ptr,
+                                     const int32_t* col_idx, const double* val, int dtype, int N, int tile,
+                                     int super_block, hgm_mat** out);
 HGM_API int hgm_mat_create_csc(hgm_ctx* ctx, int64_t rows, int64_t cols, int64_t nnz,
                                const int64_t* jc, const int64_t* ir, const double* pr,
                                int dtype, hgm_mat** out);
@@ -335,6 +350,12 @@ HGM_API int hgm_proj_norms_loop(hgm_ctx* ctx, int64_t rows, int k, const double*
  * yet: the seconds its build took, a 64-bit FNV-1a checksum over every plan array (so two builds
  * can be compared byte for byte), the partial slots, and whether the device built the ray sets
  * (HGM_OPT_FUSED_PLAN_DEV).  HGM_E_ARG when the pair has no plan (two-pass path). */
+/* The compact value stream of the pair's one-pass plan (HGM_OPT_FUSED_VSTREAM; the plan is built if
+ * needed): *active 1 when the pass reads it, *coverage the share of B's entries that carry a code,
+ * *value_bytes the bytes of the compact values (0 when inactive), *plan_bytes the device bytes of
+ * the whole plan.  Any output may be NULL. */
+HGM_API int hgm_fused_vstream_info(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, int* active, double* coverage,
+                                   int64_t* value_bytes, int64_t* plan_bytes);
 HGM_API int hgm_fused_plan_info(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, double* build_s,
                                 uint64_t* checksum, int64_t* nslot, int* device_built);
 
