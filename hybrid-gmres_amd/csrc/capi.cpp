@@ -511,6 +511,7 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
             case HGM_OPT_FUSED_ACC32: variant = v != 1; break;
             case HGM_OPT_FUSED_REDUCE: variant = !(v == 0 || v == 1); break;
             case HGM_OPT_FUSED_ROWPAIR: variant = !(v == 0 || v == 4); break;
+            case HGM_OPT_FUSED_VSDEPTH: variant = (v == 2 || v == 3 || v == 4) && !(v == 2 || v == HGM_VSDEPTH_DEFAULT); break;
             default: break;
         }
         if (variant) return bad("a measured variant of the one-pass kernel: experiments build only (HGM_EXPERIMENTS=1)");
@@ -598,6 +599,10 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
             if (!(v == 0 || v == 1 || v == 2 || v == 3)) return bad("fused_vstream is 0 to 3");
             n.fused_vstream = (int)v;
             break;
+        case HGM_OPT_FUSED_VSDEPTH:
+            if (!(v == 2 || v == 3 || v == 4)) return bad("fused_vsdepth is 2, 3 or 4");
+            n.fused_vsdepth = (int)v;
+            break;
         case HGM_OPT_LSQR_RES_IMG: if (!b01) return bad("lsqr_res_img is 0 or 1"); n.lsqr_res_img = v != 0; break;
         case HGM_OPT_LSMR_FUSE_NMON: if (!b01) return bad("lsmr_fuse_nmon is 0 or 1"); n.lsmr_fuse_nmon = v != 0; break;
         case HGM_OPT_HOST_SPIN_US:
@@ -647,6 +652,7 @@ HGM_API int hgm_ctx_get_option(const hgm_ctx* c, int option, double* v) {
         case HGM_OPT_FUSED_REDUCE: *v = n.fused_reduce; break;
         case HGM_OPT_FUSED_ROWPAIR: *v = n.fused_rowpair; break;
         case HGM_OPT_FUSED_VSTREAM: *v = n.fused_vstream; break;
+        case HGM_OPT_FUSED_VSDEPTH: *v = n.fused_vsdepth; break;
         case HGM_OPT_LSQR_RES_IMG: *v = n.lsqr_res_img; break;
         case HGM_OPT_LSMR_FUSE_NMON: *v = n.lsmr_fuse_nmon; break;
         case HGM_OPT_HOST_SPIN_US: *v = g_host_spin_us.load(); break;

@@ -1027,33 +1027,69 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
                 P[2 * u + 1] = isA ? T(0) : p;
             }
         } else if constexpr (VS) {
+            // Four phases per batch, so the 24 LDS reads fly together instead of in short groups
+            // with a wait each (two waves per SIMD: nobody else hides an LDS round trip):
+            //   1 every address of the 4 units from their slot words;
+            //   2 the 8 table reads, then the 16 q reads, back to back;
+            //   3 the decode adds once the table entries are in, then each unit's FMAs behind a
+            //     counted wait for that unit's q values (the LDS returns in order);
+            //   4 the butterfly and the accumulator adds, below.
+            // The empty asm statements pin an operand to its phase: they are ordered with the
+            // sched_barriers, which the values themselves are not.  The arithmetic is unchanged
+            // (entry 0 then entry 1 per lane and unit).
             const uint32_t dm = (uint32_t)(MAXR - 64 + ln) * (uint32_t)ES;
+            uint32_t c8[G / 2][EPL];
 #pragma unroll
             for (int u = 0; u < G / 2; ++u) {
                 const int la = b.len[2 * u];
                 // (a unit that does not exist: every lane on its dummy, as the plan pads a unit's end)
                 const uint32_t s = b.off[2 * u] ? b.s[u][0] : (dm | (dm << 16) | 0xc007c007u);
-                T pa = T(0), pb = T(0);
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) {
                     const bool inA = 2 * ln + e < la;
                     const uint32_t sl = (e ? s >> 16 : s) & 0x3ff8u;
                     // the code's table offset ((31 - code) * 8): bits 14-18 of the word, or bits 30-31 | 0-2
-                    const uint32_t c8 = (e ? __builtin_amdgcn_alignbit(s, s, 27) : s >> 11) & 0xf8u;
-                    const T v = b.v[u][0][e] + *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + VTAB * ES + c8);
-                    b.v[u][0][e] = v;
-                    const uint32_t ka = inA ? sl : dm, kk = inA ? dm : sl;
-                    const T qa = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + ka);
-                    const T qb = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + kk);
+                    c8[u][e] = (e ? __builtin_amdgcn_alignbit(s, s, 27) : s >> 11) & 0xf8u;
+                    k[u][0][e] = inA ? sl : dm;
+                    kb[u][e] = inA ? dm : sl;
+                    asm volatile("" : "+v"(c8[u][e]), "+v"(k[u][0][e]), "+v"(kb[u][e]));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            T tb[G / 2][EPL], qa[G / 2][EPL], qb[G / 2][EPL];
+#pragma unroll
+            for (int u = 0; u < G / 2; ++u)
+#pragma unroll
+                for (int e = 0; e < EPL; ++e)
+                    tb[u][e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + VTAB * ES + c8[u][e]);
+#pragma unroll
+            for (int u = 0; u < G / 2; ++u)
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) {
+                    qa[u][e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + k[u][0][e]);
+                    qb[u][e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + kb[u][e]);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < G / 2; ++u) {
+                asm volatile("" : "+v"(tb[u][0]), "+v"(tb[u][EPL - 1]));
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) b.v[u][0][e] = b.v[u][0][e] + tb[u][e];
+            }
+#pragma unroll
+            for (int u = 0; u < G / 2; ++u) {
+                asm volatile("" : "+v"(qa[u][0]), "+v"(qb[u][0]), "+v"(qa[u][EPL - 1]), "+v"(qb[u][EPL - 1]));
+                T pa = T(0), pb = T(0);
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) {
+                    const T v = b.v[u][0][e];
                     if constexpr (HGM_FUSED_FMA) {
-                        pa = fma_t(v, qa, pa);
-                        pb = fma_t(v, qb, pb);
+                        pa = fma_t(v, qa[u][e], pa);
+                        pb = fma_t(v, qb[u][e], pb);
                     } else {
-                        pa = pa + v * qa;
-                        pb = pb + v * qb;
+                        pa = pa + v * qa[u][e];
+                        pb = pb + v * qb[u][e];
                     }
-                    k[u][0][e] = ka;
-                    kb[u][e] = kk;
                 }
                 P[2 * u] = pa;
                 P[2 * u + 1] = pb;
@@ -1258,7 +1294,9 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
             r[t] = load_rp(a[t], cn[t], un[t]);
             issue(b[ti], a[ti], cn[ti], r[ti], un[ti]);
             __builtin_amdgcn_sched_barrier(0);
-            process(b[t]);
+            // (compact pass: an empty batch, the round-up of the wave's batch count to a multiple
+            // of D, is skipped by a wave-uniform branch: it would add zeros and store nothing)
+            if (!VS || b[t].cnt > 0) process(b[t]);
             __builtin_amdgcn_sched_barrier(0);
         }
     } while (b[0].cnt > 0);
@@ -2189,6 +2227,20 @@ FusedPlan* fused_plan_build_rw(hgm_ctx* c, const hgm_mat* B, int R, int W, int G
     }
     std::vector<int2> runs(std::max<int32_t>(wrun.back(), 1));
     for (size_t i = 0; i < wr.size(); ++i) std::copy(wr[i].begin(), wr[i].end(), runs.begin() + wrun[i]);
+    if (std::getenv("HGM_FUSED_VERBOSE")) {
+        // batches per wave from the run table, and the empty batches a load ring of depth D adds: the
+        // loop runs max(1, ceil(batches / D)) rounds of D batches (the compact pass skips their
+        // processing, the other passes process them as no-ops)
+        int64_t nb = 0, empty[5] = {0, 0, 0, 0, 0};
+        for (size_t w = 0; w + 1 < wrun.size(); ++w) {
+            int64_t b = 0;
+            for (int i = wrun[w]; i < wrun[w + 1]; ++i) b += (runs[i].y + G - 1) / G;
+            nb += b;
+            for (int D = 2; D <= 4; ++D) empty[D] += std::max<int64_t>(1, (b + D - 1) / D) * D - b;
+        }
+        std::fprintf(stderr, "[fused rw plan] %lld waves, %lld batches; empty batches at ring depth 2: %lld, 3: %lld, 4: %lld\n",
+                     (long long)wrun.size() - 1, (long long)nb, (long long)empty[2], (long long)empty[3], (long long)empty[4]);
+    }
     if (dev_build) return fused_plan_dev_finish(c, B, R, W, G, rowpair ? rpmode : 0, es, nreg, maxlen, wrun, runs, t0);
     // region ray sets and every entry's slot among them (a dense map per thread)
     std::vector<std::vector<int32_t>> rrays(nreg);
@@ -2383,10 +2435,11 @@ static bool fused_rw_launch(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P, co
         return true;                                                                                                  \
     }
     // the compact value stream (RP 5): the plan's streams in place of B's values, lidx and row pointers
-#define HGM_RWLV(MRV)                                                                                                \
+    // (its load ring has a depth of its own, HGM_OPT_FUSED_VSDEPTH: the plan's depth stays fused_depth)
+#define HGM_RWLV(MRV, DV)                                                                                            \
     {                                                                                                                 \
         if (!dry)                                                                                                     \
-            launch(c, false, k_fused_rw<T, GK, 0, 4, MRV, 8, 1, 2, true, 0, 5>, dim3((unsigned)P->nreg), dim3(256), \
+            launch(c, false, k_fused_rw<T, GK, 0, 4, MRV, 8, 1, DV, true, 0, 5>, dim3((unsigned)P->nreg), dim3(256), \
                    (const int64_t*)P->reg_base, (const int32_t*)P->ray_tab, (const int32_t*)P->wrun,                \
                    (const int2*)P->runs, (const int64_t*)nullptr, (const T*)P->vs_vals,                             \
                    (const uint16_t*)P->vs_slots, fa.q, fa.zraw, (T*)P->part, side ? fa.xt : nullptr,                \
@@ -2411,10 +2464,25 @@ static bool fused_rw_launch(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P, co
         // for the C4/C5 shape only
         if constexpr (sizeof(T) == 8 && !GK) {
             if (P->rowpair == 4 && P->vs_on) {
-                if (MR == 1088) HGM_RWLV(1088)
-                if (MR == 1344) HGM_RWLV(1344)
-                if (MR == 1536) HGM_RWLV(1536)
-                if (MR == 2048) HGM_RWLV(2048)
+                const int VD = c->num.fused_vsdepth;
+#define HGM_RWLVD(DV)                                                                                                \
+    if (VD == DV) {                                                                                                   \
+        if (MR == 1088) HGM_RWLV(1088, DV)                                                                            \
+        if (MR == 1344) HGM_RWLV(1344, DV)                                                                            \
+        if (MR == 1536) HGM_RWLV(1536, DV)                                                                            \
+        if (MR == 2048) HGM_RWLV(2048, DV)                                                                            \
+    }
+                // the default library: depth 2 and the production depth; the experiments build: 2, 3 and 4
+                HGM_RWLVD(2)
+#if HGM_EXPERIMENTS || HGM_VSDEPTH_DEFAULT == 3
+                HGM_RWLVD(3)
+#endif
+#if HGM_EXPERIMENTS || HGM_VSDEPTH_DEFAULT == 4
+                HGM_RWLVD(4)
+#endif
+#undef HGM_RWLVD
+                if (dry) return false;
+                throw Error{HGM_E_ARG, "fused A*(B*q): no compact-stream kernel for this plan's shape and fused_vsdepth"};
             }
         }
         if (P->rowpair == 4) {

@@ -22,6 +22,11 @@
 #ifndef HGM_EXPERIMENTS
 #define HGM_EXPERIMENTS 0
 #endif
+// Load-ring depth of the compact one-pass kernel (HGM_OPT_FUSED_VSDEPTH): the default library carries
+// depth 2 and this one, the experiments build 2, 3 and 4 (DESIGN.md §3.5 has the depth table).
+#ifndef HGM_VSDEPTH_DEFAULT
+#define HGM_VSDEPTH_DEFAULT 3
+#endif
 
 namespace hgm {
 
@@ -103,6 +108,7 @@ struct Numerics {
     int fused_rowpair = 4;          // ... row-wave pass: units of two consecutive rows per chunk (k_fused_rw RP 1-4)
     int fused_vstream = 1;          // ... row-wave pass, fp64 row-pair mode 4: compact value stream with in-slot codes
                                     //     (0 plain, 1 when it saves enough bytes, 2 / 3 measurement forms; fused.hip)
+    int fused_vsdepth = HGM_VSDEPTH_DEFAULT;   // ... the compact pass's own load ring (2..4; the other passes keep fused_depth)
     int fused_reduce = 0;           // ... row-wave partial reduction: 0 by ray (rs_slot), 1 by ray band (runs;
                                     //     bitwise equal, measured 2-4% slower pass at C4, profiles/r4_c4_reduce_band_ab.jsonl)
     bool lsqr_res_img = true;       // one-pass LSQR: final residual from the A*x image (no SpMV)

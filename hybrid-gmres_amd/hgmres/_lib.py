@@ -29,7 +29,7 @@ OPTIONS = {"parity": 1, "mgs_form": 2, "mgs_single": 3, "gram_err": 4, "gram_err
            "host_spin_us": 33, "fused_rowpair": 34,
            "lsqr_res_img": 35, "lsmr_fuse_nmon": 36}
 # options from 37 on (OPTIONS is the table of options 1-36; Context.set_option / get_option take both)
-OPTIONS_37 = {"fused_vstream": 37}
+OPTIONS_37 = {"fused_vstream": 37, "fused_vsdepth": 38}
 
 
 def option_id(name):

@@ -133,7 +133,7 @@ enum hgm_ctx_option {
                                       of one: on a communicator every rank runs it on its shard, followed by
                                       the m-vector all-reduce) [1]: the kept B*q and A*(B*q) come out of one
                                       kernel (plan built on first use) */
-    /* [experiments] options 19-22, 24, 26-30 and the marked values of 32 and 34 select measured
+    /* [experiments] options 19-22, 24, 26-30 and the marked values of 32, 34 and 38 select measured
      * variants of the one-pass kernel (DESIGN.md §3.5 records each measurement): only an experiments
      * build (hgm_experiments() == 1) has their kernels; the default library accepts only the
      * production value in brackets. */
@@ -186,7 +186,11 @@ enum hgm_ctx_option {
                                       streams, 1 compact when the plan's entry bytes shrink enough (DESIGN.md
                                       §3.5; otherwise the plain plan, bit-identical to 0), 3 compact whenever
                                       the plan's shape allows it, 2 as 3 with an empty dictionary (every value
-                                      stored: the decode overhead measurement) */
+                                      stored: the decode overhead measurement) */,
+    HGM_OPT_FUSED_VSDEPTH = 38     /* ... the compact pass of option 37 only: batches in ITS load ring, 2, 3 or
+                                      4 [3] (every other pass keeps option 28's depth 2; the same bits at
+                                      every depth; 3 is 1 % faster than 2 at C4).  The default
+                                      library carries 2 and 3; [experiments] 4 (measured slower) */
 };
 
 /* Host all-reduce hook (sum, in place, host memory) used instead of RCCL for

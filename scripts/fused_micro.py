@@ -39,7 +39,8 @@ for vname in variants:
     # | d<bits> (phase-skip timing)
     mf = re.fullmatch(r"f(\d+)(?:x(\d))?(?:r(\d+))?", vname)
     # row-wave pass: waves, region, rows per batch, ring depth, pairs
-    mw = re.fullmatch(r"w(\d)r(\d+)(?:g(\d+))?(?:d(\d))?(?:p(\d))?(?:a(\d))?(?:q(\d))?", vname)
+    # (v<depth>: the compact value stream, forced on, with that depth of its own load ring)
+    mw = re.fullmatch(r"w(\d)r(\d+)(?:g(\d+))?(?:d(\d))?(?:p(\d))?(?:a(\d))?(?:q(\d))?(?:v(\d))?", vname)
     if vname.startswith("e"):                                   # row-wave pass, phase-skip timing
         o = dict(fused_ab=1, fused_kind=1, fused_dbg=int(vname[1:]), fused_acc32=1)
     elif mw:
@@ -47,6 +48,10 @@ for vname in variants:
                  fused_group=int(mw.group(3) or 8), fused_depth=int(mw.group(4) or 2),
                  fused_pairs=int(mw.group(5) or 1), fused_acc32=int(mw.group(6) or 1),
                  fused_rowpair=int(mw.group(7) or 0))
+        if mw.group(8):
+            o.update(fused_vstream=3)
+            if "fused_vsdepth" in L.OPTIONS_37 and lib.hgm_ctx_get_option(ctx.handle, 38, C.byref(C.c_double())) == 0:
+                o.update(fused_vsdepth=int(mw.group(8)))     # (a library from before option 38: its depth 2)
     elif vname == "two":
         o = dict(fused_ab=0)
     elif mf:
