@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -193,6 +194,16 @@ void read_phib(hgm_ctx* c, const double* phib, int maxit, int k, double nb, std:
     rh.add(pbh.data(), phib, sizeof(double) * maxit);
     rh.go();
     for (int i = 0; i < maxit && i <= k; ++i) res[i] = std::fabs(pbh[i]) / nb;
+}
+
+// HGM_DEVICE_PTRS: the kernels read b and x_true in place, and the reconstruction's monitors
+// (gemv_rows: z = b or x_true) load them as 16-byte element pairs.  Every pointer handed over must
+// be 16-byte aligned (hgmres.h); one that is not is refused before anything is enqueued.
+static bool device_ptrs(const hgm_opts* o, const double* b_in, const double* xt_in, const double* x_out) {
+    if (!(o && (o->flags & HGM_DEVICE_PTRS))) return false;
+    for (const double* p : {b_in, xt_in, x_out})
+        HGM_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0, "HGM_DEVICE_PTRS: b, x_true and x must be 16-byte aligned");
+    return true;
 }
 
 // Input vector hand-over: device pointer (HGM_DEVICE_PTRS) or host buffer.
@@ -386,7 +397,7 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     const long waits0 = c->waits;
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
     c->path_mon.clear();
-    const bool dev = o && (o->flags & HGM_DEVICE_PTRS);
+    const bool dev = device_ptrs(o, b_in, xt_in, x_out);
     const int orth = o ? o->orth : HGM_MGS;
     const int64_t m = A->rows, n = A->cols;
     const bool nspace = sp.side == HGM_SIDE_BA;
@@ -936,7 +947,7 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
     const bool parity = c->num.parity;   // fixed summation orders
     HGM_REQUIRE(!parity || (!dist_n(c) && po.trivial()), "parity mode: single rank, reference pixel order");
-    const bool dev = o && (o->flags & HGM_DEVICE_PTRS);
+    const bool dev = device_ptrs(o, b_in, xt_in, x_out);
     const int64_t m = A->rows, n = A->cols;
     const T* b = stage_in<T>(c, "in_b", b_in, m, dev);
     const T* xt = stage_in_n<T>(c, "in_xt", xt_in, n, dev, po);
@@ -1180,7 +1191,7 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
     HGM_REQUIRE(b_in != nullptr, "b is required");
     const bool parity = c->num.parity;   // fixed summation orders
     HGM_REQUIRE(!parity || (!dist_n(c) && po.trivial()), "parity mode: single rank, reference pixel order");
-    const bool dev = o && (o->flags & HGM_DEVICE_PTRS);
+    const bool dev = device_ptrs(o, b_in, xt_in, x_out);
     const int64_t m = A->rows, n = A->cols;
     if (maxit <= 0) maxit = (int)std::min<int64_t>(m, n);                    // :5 default min(m,n)
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
@@ -1438,7 +1449,7 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
     HGM_REQUIRE(!c->num.parity || (!dist_n(c) && po.trivial()), "parity mode: single rank, reference pixel order");
     HGM_REQUIRE(b_in != nullptr && xt_in != nullptr, "b and x_true are required");
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
-    const bool dev = o && (o->flags & HGM_DEVICE_PTRS);
+    const bool dev = device_ptrs(o, b_in, xt_in, x_out);
     const int64_t m = A->rows, n = A->cols;
     const int64_t ldv = round_up(n > 0 ? n : 1, 64);
     const double* b = stage_in<double>(c, "in_b", b_in, m, dev);

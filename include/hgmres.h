@@ -76,7 +76,9 @@ enum hgm_side { HGM_SIDE_AB = 0, HGM_SIDE_BA = 1 };
 
 /* Flags for the *_ex entry points. */
 enum hgm_flags {
-    HGM_DEVICE_PTRS = 1,       /* b, x_true, x are device pointers (inputs resident in HBM) */
+    HGM_DEVICE_PTRS = 1,       /* b, x_true, x are device pointers (inputs resident in HBM).  Each must be
+                                  16-byte aligned: the kernels read b and x_true in place as pairs of
+                                  doubles.  A pointer that is not is refused with HGM_E_ARG. */
     HGM_EXPLICIT_RESIDUAL = 2  /* BA-side GMRES: monitor norm(b - A*x) with an explicit SpMV of x
                                   instead of b - (A*Q) y from the kept operator products */
 };
