@@ -603,6 +603,7 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
             if (!(v == 2 || v == 3 || v == 4)) return bad("fused_vsdepth is 2, 3 or 4");
             n.fused_vsdepth = (int)v;
             break;
+        case HGM_OPT_PERT_SHARED: if (!b01) return bad("pert_shared is 0 or 1"); n.pert_shared = v != 0; break;
         case HGM_OPT_LSQR_RES_IMG: if (!b01) return bad("lsqr_res_img is 0 or 1"); n.lsqr_res_img = v != 0; break;
         case HGM_OPT_LSMR_FUSE_NMON: if (!b01) return bad("lsmr_fuse_nmon is 0 or 1"); n.lsmr_fuse_nmon = v != 0; break;
         case HGM_OPT_HOST_SPIN_US:
@@ -653,6 +654,7 @@ HGM_API int hgm_ctx_get_option(const hgm_ctx* c, int option, double* v) {
         case HGM_OPT_FUSED_ROWPAIR: *v = n.fused_rowpair; break;
         case HGM_OPT_FUSED_VSTREAM: *v = n.fused_vstream; break;
         case HGM_OPT_FUSED_VSDEPTH: *v = n.fused_vsdepth; break;
+        case HGM_OPT_PERT_SHARED: *v = n.pert_shared; break;
         case HGM_OPT_LSQR_RES_IMG: *v = n.lsqr_res_img; break;
         case HGM_OPT_LSMR_FUSE_NMON: *v = n.lsmr_fuse_nmon; break;
         case HGM_OPT_HOST_SPIN_US: *v = g_host_spin_us.load(); break;
@@ -1049,6 +1051,53 @@ HGM_API int hgm_spmm(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, in
     return HGM_OK;
 }
 
+// hgm_spmm's hand-over around the perturbed product; B0's stored orders serve both operators
+static void spmm_pert_impl(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs,
+                           const double* X, int64_t ldx, double* Y, int64_t ldy) {
+    HGM_HIP(hipSetDevice(c->device));
+    HGM_REQUIRE(B0->dtype == HGM_F64 && E->dtype == HGM_F64, "spmm_pert: fp64 operators only");
+    HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, "spmm_pert: 1 <= nvec <= 8");
+    HGM_REQUIRE(E->rows == B0->rows && E->cols == B0->cols, "spmm_pert: E must have B0's shape");
+    HGM_REQUIRE(E->row_order == B0->row_order && E->col_order == B0->col_order,
+                "spmm_pert: E must be stored in B0's row and column order");
+    HGM_REQUIRE(ldx >= B0->cols && ldy >= B0->rows, "spmm_pert: ldx >= cols and ldy >= rows");
+    for (int r = 0; r < nvec; ++r) HGM_REQUIRE(std::isfinite(coefs[r]), "spmm_pert: every coefficient must be finite");
+    const int NV = spmm_width(nvec);
+    const int64_t rows = B0->rows, cols = B0->cols;
+    const bool shared = c->num.pert_shared && same_pattern(c, B0, E);
+    double* Xi = c->buf<double>("spmm_xi", (size_t)(cols > 0 ? cols : 1) * NV);
+    double* Yi = c->buf<double>("spmm_yi", (size_t)(rows > 0 ? rows : 1) * NV);
+    double* xp = B0->col_order.trivial() ? nullptr : c->buf<double>("spmm_x_pix", (size_t)cols * nvec);
+    double* yp = B0->row_order.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
+    MvCols src, dst;
+    for (int r = 0; r < SPMM_MAXV; ++r) src.p[r] = dst.p[r] = nullptr;
+    hipEvent_t tm;
+    timing_begin(c, KC_SPMM, &tm);
+    for (int r = 0; r < nvec; ++r) {
+        src.p[r] = const_cast<double*>(X) + r * ldx;
+        if (xp) {
+            pix_permute<double>(c, B0->col_order, X + r * ldx, xp + (size_t)r * cols, 0);
+            src.p[r] = xp + (size_t)r * cols;
+        }
+        dst.p[r] = yp ? yp + (size_t)r * rows : Y + r * ldy;
+    }
+    mv_pack(c, cols, nvec, src, Xi);
+    spmm_pert(c, B0, E, shared, nvec, coefs, Xi, Yi);
+    mv_unpack(c, rows, nvec, Yi, dst);
+    if (yp)
+        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, B0->row_order, yp + (size_t)r * rows, Y + r * ldy, 1);
+    // the kernel's streams (shared: 20 B/entry; general: 12 B/entry of each operator) and the interleaved vectors
+    timing_end(c, KC_SPMM, tm,
+               (shared ? 20.0 * (double)B0->nnz : 12.0 * ((double)B0->nnz + (double)E->nnz)) + 8.0 * NV * (rows + cols));
+}
+
+HGM_API int hgm_spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs,
+                          const double* X, int64_t ldx, double* Y, int64_t ldy) {
+    if (!c || !B0 || !E || !coefs || !X || !Y) return HGM_E_ARG;
+    HGM_TRY(c, spmm_pert_impl(c, B0, E, nvec, coefs, X, ldx, Y, ldy));
+    return HGM_OK;
+}
+
 HGM_API int hgm_proj_norms(hgm_ctx* c, int64_t rows, int k, const double* V, int64_t ldv, const double* Y,
                            int64_t ldy, int nlam, const double* t, double* sumsq_diff, double* sumsq) {
     if (!c || !V || !Y || !sumsq_diff) return HGM_E_ARG;
@@ -1192,6 +1241,15 @@ HGM_API int hgm_gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat*
     HGM_SOLVE(c, gmres_bounds_batch(c, o, A, B, Bm, ldb, nrhs, xt, ldxt, tol, maxit, lambdas, side, hybrid ? 1 : 0, X,
                                     ldx, err, res, niters, col_status));
 }
+HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0,
+                                      const hgm_mat* E, const double* coefs, int ncoef, const double* b,
+                                      const double* xt, double tol, int maxit, const double* lambdas, int side,
+                                      int hybrid, double* X, int64_t ldx, double* err, double* res, int* niters,
+                                      int* col_status) {
+    if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
+    HGM_SOLVE(c, gmres_bounds_mismatch(c, o, A, B0, E, coefs, ncoef, b, xt, tol, maxit, lambdas, side, hybrid ? 1 : 0,
+                                       X, ldx, err, res, niters, col_status));
+}
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b,
                                const double* xt, double tol, int maxit, double* x, double* err, double* res,
                                int* niters) {
@@ -1247,6 +1305,13 @@ HGM_API int hgm_arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const do
                         double breakdown_tol, int orth, double* H, double* beta, int* kdone) {
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
     HGM_SOLVE(c, arnoldi(c, A, B, b, k, side, breakdown_tol, orth, H, beta, kdone));
+}
+
+HGM_API int hgm_arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
+                                 const double* coefs, int ncoef, const double* b, int k, int side,
+                                 double breakdown_tol, int orth, double* H, double* beta, int* kdone) {
+    if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
+    HGM_SOLVE(c, arnoldi_mismatch(c, A, B0, E, coefs, ncoef, b, k, side, breakdown_tol, orth, H, beta, kdone));
 }
 
 HGM_API int hgm_gcv_from_H(const double* H, int k, double beta, double lambda, double trace_m, double* gcv) {

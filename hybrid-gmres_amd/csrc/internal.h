@@ -113,7 +113,8 @@ struct Numerics {
                                     //     bitwise equal, measured 2-4% slower pass at C4, profiles/r4_c4_reduce_band_ab.jsonl)
     bool lsqr_res_img = true;       // one-pass LSQR: final residual from the A*x image (no SpMV)
     bool lsmr_fuse_nmon = true;     // one-pass fp32 LSMR: the n-space step and monitor in one launch
-    int krylov_pad = -1;            // Krylov basis column padding (elements; -1 auto, kernels.hip krylov_ld)
+    bool pert_shared = true;        // perturbed product: shared index stream when E has B0's pattern (spmm.hip)
+    int krylov_pad = -1;           // Krylov basis column padding (elements; -1 auto, kernels.hip krylov_ld)
     int fused_dbg = 0;              // ... timing experiments: skip phases (wrong results)
 };
 struct FusedPlan;
@@ -374,6 +375,14 @@ int spmm_width(int nvec);
 void mv_pack(hgm_ctx* c, int64_t n, int nvec, const MvCols& src, double* Xi);
 void mv_unpack(hgm_ctx* c, int64_t n, int nvec, const double* Yi, const MvCols& dst, bool last = false);
 void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi);
+// Perturbed product (spmm.hip k_spmm_pert): slot r of Yi = B0 Xi(:,r) + coefs[r] * (E Xi(:,r)), B0's and
+// E's entries read once for all slots; E has B0's shape.  shared: E also has B0's rp / ci (same_pattern),
+// so the index stream and the gathers are shared; either way a slot's bits depend on the row, B0->group
+// and its coefficient only, and the two paths agree bit for bit.  same_pattern compares the index
+// streams on the device (one pass, one host read).
+bool same_pattern(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E);
+void spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, bool shared, int nvec, const double* coefs,
+               const double* Xi, double* Yi);
 
 // MGS sweep of v = Q(:,kk+1) against Q(:,0..kk); writes Hcol[0..kk+1] (device) and
 // normalises Q(:,kk+1) unless H(kk+1,kk) == 0.  dist: n-vectors sharded (scalar all-reduce
@@ -768,6 +777,13 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                        int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
                        const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
                        double* res_hist, int* niters, int* col_status);
+int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
+                          const double* coefs, int ncoef, const double* b, const double* xt_in, double tol, int maxit,
+                          const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
+                          double* res_hist, int* niters, int* col_status);
+int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs,
+                     int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
+                     double* beta_out, int* kdone);
 int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
                         const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
                         const hgm_mat* dML, const hgm_mat* dMR, int ritz_steps, double* x_out, double* err_out,

@@ -1761,33 +1761,36 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
 // column is packed into, and every other kernel runs per column with scratch of its own, so a
 // column's bits do not depend on its neighbours (which is why even one column takes the spmm route
 // and never the one-pass plan).
-int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
-                       int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
-                       const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
-                       double* res_hist, int* niters, int* col_status) {
-    check_dims(A, B);
-    solver_guard(c);
-    HGM_REQUIRE(B != nullptr, "B is NULL");
-    HGM_REQUIRE(A->dtype == HGM_F64, "batched solve: fp64 operators only");
-    if (dist_n(c) || c->host_ar != nullptr)
-        throw Error{HGM_E_UNSUPPORTED, "batched solve: single rank only (no communicator / all-reduce hook)"};
-    HGM_REQUIRE(!c->num.parity, "batched solve: not in parity mode");
-    HGM_REQUIRE(!(o && (o->flags & HGM_DEVICE_PTRS)), "batched solve: host buffers only (HGM_DEVICE_PTRS refused)");
-    HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, "batched solve: 1 <= nrhs <= 64");
-    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
-    HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
+//
+// lockstep_core is that loop; its callers differ in two things (Lockstep):
+//  * the column's right-hand side: column j of a matrix (hgm_gmres_bounds_batch) or one b shared by
+//    every column (the mismatch sweep);
+//  * the B pass: spmm(B) for every column, or the perturbed product (spmm.hip k_spmm_pert) in which
+//    column j applies B + coefs[j] * E, the coefficients packed with the running columns as they are
+//    regrouped.  The A pass is spmm(A) either way.
+// With arnoldi set it is the GCV Arnoldi of gcv_function.m:3-33 per column instead of a solve: no
+// projected solve, no monitors and no kept products; a column leaves at H(k+1,k) < btol (:30) with
+// niters[j] = the steps done (hgm_arnoldi's kdone).
+namespace {
+struct Lockstep {
+    const double* rhs = nullptr;         // column j's right-hand side: rhs + ldrhs * j (host)
+    int64_t ldrhs = 0;                   // 0: one b shared by every column
+    const hgm_mat* E = nullptr;          // perturbed B pass (nullptr: spmm(B))
+    const double* coefs = nullptr;       // ... column j's coefficient
+    bool arnoldi = false;
+    double btol = 0.0;                   // arnoldi: the break threshold
+    double* beta_out = nullptr;          // arnoldi: ||r0|| per column
+};
+
+int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const hgm_mat* A, const hgm_mat* B,
+                  int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit, const double* lambdas, int side,
+                  int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, int* niters,
+                  int* col_status) {
     const int64_t m = A->rows, n = A->cols;
-    HGM_REQUIRE(ldb >= m, "batched solve: ldb >= rows(A)");
-    HGM_REQUIRE(X_out == nullptr || ldx >= n, "batched solve: ldx >= cols(A)");
-    HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, "batched solve: ldxt is 0 (one shared x_true) or >= cols(A)");
-    if (hybrid) {
-        HGM_REQUIRE(lambdas != nullptr, "batched solve: lambdas are required with hybrid = 1");
-        for (int j = 0; j < nrhs; ++j)
-            HGM_REQUIRE(std::isfinite(lambdas[j]) && lambdas[j] >= 0.0,
-                        "batched solve: every lambda must be finite and >= 0");
-    }
     const PixOrder po = n_order(c, A, B);
-    const int orth = o ? o->orth : HGM_MGS;
+    const bool pert = L.E != nullptr;
+    // E on B's pattern: one compare pass over the index streams per solve
+    const bool pert_shared = pert && c->num.pert_shared && same_pattern(c, B, L.E);
     const bool nspace = side == HGM_SIDE_BA;
     const int64_t dim = nspace ? n : m;
     const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
@@ -1803,10 +1806,14 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     double* Qall = kb.Q;
     const int64_t ldq = kb.ld;
     const size_t qs = (size_t)ldq * (maxit + 1);            // one column's basis
-    // kept products: BA: W = A*Q ; AB: V = B*Q and W = A*B*Q  (the sweep's, per column)
-    double* Wall = c->buf<double>("bt_W", (size_t)ldm * maxit * nrhs);
-    double* Vall = nspace ? nullptr : c->buf<double>("bt_V", (size_t)ldn * maxit * nrhs);
-    double* ball = c->buf<double>("bt_b", (size_t)ldm * nrhs);
+    // kept products: BA: W = A*Q ; AB: V = B*Q and W = A*B*Q  (the sweep's, per column).  The Arnoldi
+    // keeps none: AB needs the current A*B*q alone (one vector per column), BA nothing.
+    const int kept = L.arnoldi ? 1 : maxit;
+    auto kslot = [&](int k) { return L.arnoldi ? 0 : k; };
+    double* Wall = c->buf<double>("bt_W", (size_t)ldm * kept * nrhs);
+    double* Vall = nspace || L.arnoldi ? nullptr : c->buf<double>("bt_V", (size_t)ldn * kept * nrhs);
+    const int nb_cols = L.ldrhs == 0 ? 1 : nrhs;
+    double* ball = c->buf<double>("bt_b", (size_t)ldm * nb_cols);
     const int nxt_cols = xt_in ? (ldxt == 0 ? 1 : nrhs) : 1;
     double* xtall = c->buf<double>("bt_xt", (size_t)ldn * nxt_cols);
     double* xall = c->buf<double>("bt_x", (size_t)ldn * nrhs);
@@ -1821,14 +1828,14 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                 c->buf<double>("bt_in1", (size_t)(n > 0 ? n : 1) * SPMM_MAXV)};
     HGM_HIP(hipMemsetAsync(Hd, 0, sizeof(double) * hs * nrhs, c->stream));
     auto Qj = [&](int j) { return Qall + qs * (size_t)j; };
-    auto Wj = [&](int j) { return Wall + (size_t)ldm * maxit * j; };
-    auto Vj = [&](int j) -> const double* { return nspace ? Qj(j) : Vall + (size_t)ldn * maxit * j; };
+    auto Wj = [&](int j) { return Wall + (size_t)ldm * kept * j; };
+    auto Vj = [&](int j) -> const double* { return nspace ? Qj(j) : Vall + (size_t)ldn * kept * j; };
     const int64_t ldv = nspace ? ldq : ldn;
-    auto bj = [&](int j) { return ball + (size_t)ldm * j; };
+    auto bj = [&](int j) { return ball + (size_t)ldm * (nb_cols == 1 ? 0 : j); };
     auto xtj = [&](int j) -> const double* { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
     auto xj = [&](int j) { return xall + (size_t)ldn * j; };
 
-    for (int j = 0; j < nrhs; ++j) h2d(c, bj(j), Bm + (size_t)ldb * j, sizeof(double) * m);
+    for (int j = 0; j < nb_cols; ++j) h2d(c, bj(j), L.rhs + (size_t)L.ldrhs * j, sizeof(double) * m);
     if (xt_in) {
         // x_true in the reference order, permuted into the operators' stored pixel order
         double* tmp = po.trivial() ? nullptr : c->buf<double>("bt_xt_ref", n > 0 ? n : 1);
@@ -1853,13 +1860,30 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     auto operator_pass = [&](const std::vector<int>& cols, size_t g0, int nv, const hgm_mat* first,
                              const hgm_mat* second, auto src, auto mid, auto dst) {
         MvCols ts, tm, td;
-        for (int r = 0; r < SPMM_MAXV; ++r) ts.p[r] = tm.p[r] = td.p[r] = nullptr;
+        double cf[SPMM_MAXV];                                    // the group's coefficients, packed as its columns
+        for (int r = 0; r < SPMM_MAXV; ++r) {
+            ts.p[r] = tm.p[r] = td.p[r] = nullptr;
+            cf[r] = 0.0;
+        }
         for (int r = 0; r < nv; ++r) {
             const int j = cols[g0 + r];
             ts.p[r] = const_cast<double*>(src(j));
             tm.p[r] = mid(j);
             td.p[r] = dst(j);
+            if (pert) cf[r] = L.coefs[j];
         }
+        double bytes = 0.0;
+        // one pass of the pair: spmm(A), and for B either spmm(B) or the perturbed product
+        auto product = [&](const hgm_mat* M, const double* in, double* out) {
+            const double vec_bytes = 8.0 * spmm_width(nv) * (M->rows + M->cols);
+            if (M == B && pert) {
+                spmm_pert(c, B, L.E, pert_shared, nv, cf, in, out);
+                bytes += (pert_shared ? 20.0 * B->nnz : 12.0 * ((double)B->nnz + L.E->nnz)) + vec_bytes;
+            } else {
+                spmm(c, M, nv, in, out);
+                bytes += 12.0 * M->nnz + vec_bytes;
+            }
+        };
         hipEvent_t tev = nullptr;
         timing_begin(c, KC_SPMM, &tev);
         // first: cols(first) -> rows(first) ; second: rows(first) = cols(second) -> rows(second)
@@ -1867,14 +1891,12 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         double* I0 = from_m ? Im[0] : In[0];
         double* I1 = from_m ? In[0] : Im[0];
         mv_pack(c, first->cols, nv, ts, I0);
-        spmm(c, first, nv, I0, I1);
+        product(first, I0, I1);
         if (tm.p[0]) mv_unpack(c, first->rows, nv, I1, tm);
-        double bytes = 12.0 * first->nnz + 8.0 * spmm_width(nv) * (first->rows + first->cols);
         if (second) {
             double* I2 = from_m ? Im[1] : In[1];
-            spmm(c, second, nv, I1, I2);
+            product(second, I1, I2);
             mv_unpack(c, second->rows, nv, I2, td);
-            bytes += 12.0 * second->nnz + 8.0 * spmm_width(nv) * (second->rows + second->cols);
         }
         timing_end(c, KC_SPMM, tev, bytes);
     };
@@ -1923,12 +1945,15 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
             const int nv = (int)std::min<size_t>(SPMM_MAXV, act.size() - g0);
             auto qk = [&](int j) { return (const double*)(Qj(j) + (int64_t)k * ldq); };
             if (nspace)    // A*q kept, B*(A*q) is the new basis vector
-                operator_pass(act, g0, nv, A, B, qk, [&](int j) { return Wj(j) + (int64_t)k * ldm; },
+                operator_pass(act, g0, nv, A, B, qk,
+                              [&](int j) { return L.arnoldi ? (double*)nullptr : Wj(j) + (int64_t)k * ldm; },
                               [&](int j) { return Qj(j) + (int64_t)(k + 1) * ldq; });
             else           // B*q and A*(B*q) kept; the latter is orthogonalised into the new basis vector
                 operator_pass(act, g0, nv, B, A, qk,
-                              [&](int j) { return const_cast<double*>(Vj(j)) + (int64_t)k * ldn; },
-                              [&](int j) { return Wj(j) + (int64_t)k * ldm; });
+                              [&](int j) {
+                                  return L.arnoldi ? (double*)nullptr : const_cast<double*>(Vj(j)) + (int64_t)k * ldn;
+                              },
+                              [&](int j) { return Wj(j) + (int64_t)kslot(k) * ldm; });
         }
         // ---- orthogonalisation (:26-32), the single solver's sweep once per running column ----
         for (int j : act) {
@@ -1937,7 +1962,7 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
             double* v = Q + (int64_t)(k + 1) * ldq;
             const double* src = nullptr;
             if (!nspace) {
-                const double* w = Wj(j) + (int64_t)k * ldm;
+                const double* w = Wj(j) + (int64_t)kslot(k) * ldm;
                 if (orth == HGM_CGS2)
                     HGM_HIP(hipMemcpyAsync(v, w, sizeof(double) * m, hipMemcpyDeviceToDevice, c->stream));
                 else src = w;
@@ -1956,6 +1981,15 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
         const int kk = k + 1;
         next.clear();
         ran.clear();
+        if (L.arnoldi) {
+            // gcv_function.m:30: the step counts, and the column breaks before Q(:,k+1) = v / H(k+1,k)
+            for (int j : act) {
+                niters[j] = kk;
+                if (!(Hh(j, k + 1, k) < L.btol)) next.push_back(j);
+            }
+            act.swap(next);
+            continue;
+        }
         for (int j : act) {
             if (Hh(j, k + 1, k) == 0) {                          // :31  breakdown of this column
                 // the single solver's convention: niters = k + 1, history entry k stays 0, x is the
@@ -2004,10 +2038,112 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
     if (X_out)
         for (int j = 0; j < nrhs; ++j)
             if (x_assigned[j]) stage_out_n<double>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
-    if (o && o->H_out) std::memcpy(o->H_out, H.data(), sizeof(double) * H.size());
+    if (H_out) std::memcpy(H_out, H.data(), sizeof(double) * H.size());
+    if (L.beta_out) std::copy(beta.begin(), beta.end(), L.beta_out);
     if (unassigned)
         throw Error{HGM_E_NOT_ASSIGNED, "Output argument \"x\" not assigned in at least one column (breakdown at k = 1)"};
     return HGM_OK;
+}
+
+// the refusals every lockstep entry point shares
+void lockstep_guard(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const std::string& what) {
+    check_dims(A, B);
+    solver_guard(c);
+    HGM_REQUIRE(B != nullptr, "B is NULL");
+    HGM_REQUIRE(A->dtype == HGM_F64, what + ": fp64 operators only");
+    if (dist_n(c) || c->host_ar != nullptr)
+        throw Error{HGM_E_UNSUPPORTED, what + ": single rank only (no communicator / all-reduce hook)"};
+    HGM_REQUIRE(!c->num.parity, what + ": not in parity mode");
+    HGM_REQUIRE(!(o && (o->flags & HGM_DEVICE_PTRS)), what + ": host buffers only (HGM_DEVICE_PTRS refused)");
+}
+
+void lockstep_lambdas(const double* lambdas, int ncols, int hybrid, const std::string& what) {
+    if (!hybrid) return;
+    HGM_REQUIRE(lambdas != nullptr, what + ": lambdas are required with hybrid = 1");
+    for (int j = 0; j < ncols; ++j)
+        HGM_REQUIRE(std::isfinite(lambdas[j]) && lambdas[j] >= 0.0, what + ": every lambda must be finite and >= 0");
+}
+
+// E and the coefficients of a mismatch sweep against its B0
+void mismatch_guard(const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs, int ncoef,
+                    const std::string& what) {
+    HGM_REQUIRE(E != nullptr, what + ": E is NULL");
+    HGM_REQUIRE(E->dtype == HGM_F64, what + ": fp64 operators only");
+    HGM_REQUIRE(A != B0 && E != A, what + ": A, B0 and E must be distinct operators");
+    HGM_REQUIRE(E->rows == B0->rows && E->cols == B0->cols, what + ": E must have B0's shape");
+    HGM_REQUIRE(E->row_order == B0->row_order && E->col_order == B0->col_order,
+                what + ": E must be stored in B0's row and column order");
+    HGM_REQUIRE(ncoef >= 1 && ncoef <= 64, what + ": 1 <= ncoef <= 64");
+    HGM_REQUIRE(coefs != nullptr, what + ": coefs is required");
+    for (int j = 0; j < ncoef; ++j) HGM_REQUIRE(std::isfinite(coefs[j]), what + ": every coefficient must be finite");
+}
+}  // namespace
+
+int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
+                       int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
+                       const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
+                       double* res_hist, int* niters, int* col_status) {
+    const std::string what = "batched solve";
+    lockstep_guard(c, o, A, B, what);
+    HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, "batched solve: 1 <= nrhs <= 64");
+    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+    HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
+    const int64_t m = A->rows, n = A->cols;
+    HGM_REQUIRE(ldb >= m, "batched solve: ldb >= rows(A)");
+    HGM_REQUIRE(X_out == nullptr || ldx >= n, "batched solve: ldx >= cols(A)");
+    HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, "batched solve: ldxt is 0 (one shared x_true) or >= cols(A)");
+    lockstep_lambdas(lambdas, nrhs, hybrid, what);
+    Lockstep L;
+    L.rhs = Bm;
+    L.ldrhs = ldb > 0 ? ldb : 1;                              // never 0 (one shared b), also with m == 0
+    return lockstep_core(c, L, o ? o->orth : HGM_MGS, o ? o->H_out : nullptr, A, B, nrhs, xt_in, ldxt, tol, maxit,
+                         lambdas, side, hybrid, X_out, ldx, err_hist, res_hist, niters, col_status);
+}
+
+// plot_error_vs_mismatch_norm.m:23-61 / run_2D_phantom.m:79-102: column j is the *_bounds solve of the
+// one b with the back-projector B0 + coefs[j] * E.  No such operator is formed: B0 and E are read once
+// per group of up to 8 running levels (spmm.hip k_spmm_pert).
+int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
+                          const double* coefs, int ncoef, const double* b, const double* xt_in, double tol, int maxit,
+                          const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
+                          double* res_hist, int* niters, int* col_status) {
+    const std::string what = "mismatch sweep";
+    lockstep_guard(c, o, A, B0, what);
+    mismatch_guard(A, B0, E, coefs, ncoef, what);
+    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+    HGM_REQUIRE(b != nullptr && niters != nullptr, "b and niters are required");
+    HGM_REQUIRE(X_out == nullptr || ldx >= A->cols, what + ": ldx >= cols(A)");
+    lockstep_lambdas(lambdas, ncoef, hybrid, what);
+    Lockstep L;
+    L.rhs = b;
+    L.E = E;
+    L.coefs = coefs;
+    return lockstep_core(c, L, o ? o->orth : HGM_MGS, o ? o->H_out : nullptr, A, B0, ncoef, xt_in, 0, tol, maxit,
+                         lambdas, side, hybrid, X_out, ldx, err_hist, res_hist, niters, col_status);
+}
+
+// gcv_function.m:3-33 for every level of a mismatch sweep in lockstep (the two GCV Arnoldis of
+// plot_error_vs_mismatch_norm.m:46-50): H holds ncoef consecutive (k+1) x k blocks.
+int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs,
+                     int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
+                     double* beta_out, int* kdone) {
+    const std::string what = "mismatch Arnoldi";
+    lockstep_guard(c, nullptr, A, B0, what);
+    mismatch_guard(A, B0, E, coefs, ncoef, what);
+    HGM_REQUIRE(kg >= 1, "k must be >= 1");
+    HGM_REQUIRE(b != nullptr, "b is required");
+    std::vector<int> done(ncoef, 0);
+    Lockstep L;
+    L.rhs = b;
+    L.E = E;
+    L.coefs = coefs;
+    L.arnoldi = true;
+    L.btol = btol;
+    L.beta_out = beta_out;
+    const int st = lockstep_core(c, L, orth, H_out, A, B0, ncoef, nullptr, 0, 0.0, kg, nullptr, side, 0, nullptr, 0,
+                                 nullptr, nullptr, done.data(), nullptr);
+    if (kdone) std::copy(done.begin(), done.end(), kdone);
+    return st;
 }
 
 // explicit instantiations used by capi.cpp

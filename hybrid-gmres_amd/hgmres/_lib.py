@@ -29,7 +29,7 @@ OPTIONS = {"parity": 1, "mgs_form": 2, "mgs_single": 3, "gram_err": 4, "gram_err
            "host_spin_us": 33, "fused_rowpair": 34,
            "lsqr_res_img": 35, "lsmr_fuse_nmon": 36}
 # options from 37 on (OPTIONS is the table of options 1-36; Context.set_option / get_option take both)
-OPTIONS_37 = {"fused_vstream": 37, "fused_vsdepth": 38}
+OPTIONS_37 = {"fused_vstream": 37, "fused_vsdepth": 38, "pert_shared": 39}
 
 
 def option_id(name):
@@ -95,6 +95,7 @@ _SIGS = {
     "hgm_spmv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgm_spmv_ab": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgm_spmm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64]),
+    "hgm_spmm_pert": (c_int, [c_void_p, c_void_p, c_void_p, c_int, dp, c_void_p, c_int64, c_void_p, c_int64]),
     "hgm_proj_norms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp, dp]),
     "hgm_proj_norms_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp]),
     "hgm_fused_plan_info": (c_int, [c_void_p, c_void_p, c_void_p, dp, P(C.c_uint64), ip64, P(c_int)]),
@@ -117,6 +118,10 @@ _SIGS = {
                                        dp, dp, dp, dp, P(c_int), P(c_int)]),
     "hgm_gmres_bounds_batch": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, c_int64, c_int, dp, c_int64, c_double,
                                        c_int, dp, c_int, c_int, dp, c_int64, dp, dp, P(c_int), P(c_int)]),
+    "hgm_gmres_bounds_mismatch": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, c_void_p, dp, c_int, dp, dp, c_double,
+                                          c_int, dp, c_int, c_int, dp, c_int64, dp, dp, P(c_int), P(c_int)]),
+    "hgm_arnoldi_mismatch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, dp, c_int, dp, c_int, c_int, c_double, c_int,
+                                     dp, dp, P(c_int)]),
     "hgm_lsqr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, P(c_int)]),
     "hgm_lsmr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, dp, P(c_int)]),
     "hgm_arnoldi": (c_int, [c_void_p, c_void_p, c_void_p, dp, c_int, c_int, c_double, c_int, dp, dp, P(c_int)]),

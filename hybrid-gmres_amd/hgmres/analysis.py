@@ -188,3 +188,80 @@ def error_vs_noise_level(A, B, b_exact, x_true, noise_levels, *, maxit, tol=1e-6
         out[f"final_errors_{key}"] = fin
         out[f"niters_{key}"] = nit
     return out
+
+
+def _fro(E):
+    """``norm(E, 'fro')`` of a scipy matrix, an array or a device operator."""
+    if isinstance(E, core.SparseOperator):
+        E = E.to_scipy()
+    if hasattr(E, "data") and hasattr(E, "tocsr"):
+        return float(np.linalg.norm(E.tocsr().data))
+    return float(np.linalg.norm(np.asarray(E, dtype=np.float64)))
+
+
+def error_vs_mismatch_norm(A, B0, E, b, x_true, c_range, *, maxit, tol=1e-6, k_gcv=20, lambdas=None,
+                           solvers=("hab", "hba"), ctx=None) -> dict:
+    """The numeric part of ``plot_error_vs_mismatch_norm.m:23-61`` (and, with all four ``solvers``, of
+    ``run_2D_phantom.m:79-102``): the final errors of the ``*_bounds`` solvers over a range of back-projector
+    mismatch levels ``B_pert = B0 + c * E`` for one fixed ``E``, every solver's loop over the levels as ONE
+    lockstep solve (:func:`hgmres.core.gmres_bounds_mismatch`) and the GCV Arnoldis of all levels as one
+    lockstep Arnoldi per side (:func:`hgmres.core.arnoldi_mismatch`).  No ``B_pert`` is formed or uploaded:
+    ``B0`` and ``E`` are read once per group of up to 8 levels.
+
+    ``b`` is the (noisy) right-hand side shared by every level.  The hybrid solvers' lambdas are the GCV
+    minimisers of ``:46-50`` (``gcv_fminbnd`` on [1e-9, 1e-1] with TolX 1e-8 on each level's H) unless
+    ``lambdas = (lambdas_ab, lambdas_ba)`` supplies them.  ``solvers`` picks from 'hab', 'hba' (the hybrid
+    solvers of ``:53-56``) and 'nab', 'nba' (the non-hybrid ones).  Calls take at most 64 levels each.
+
+    Returns ``c_range``, ``mismatch_norms = |c| * ||E||_F`` (``:36``), ``lambda_gcv_ab`` / ``lambda_gcv_ba`` (NaN
+    for a side no hybrid solver asked for and no ``lambdas`` gave) and, per solver key, ``final_errors_<key>``
+    (``err(end)``, ``:54,57``) and ``niters_<key>``."""
+    cr = np.asarray(c_range, dtype=np.float64).reshape(-1)
+    nl = cr.size
+    if nl < 1:
+        raise ValueError("c_range is empty")
+    if not np.all(np.isfinite(cr)):
+        raise ValueError("c_range: every level must be finite")
+    keys = {"hab": ("ab", True), "hba": ("ba", True), "nab": ("ab", False), "nba": ("ba", False)}
+    solvers = tuple(solvers)
+    if not solvers or any(s not in keys for s in solvers):
+        raise ValueError(f"solvers: a non-empty choice of {sorted(keys)}, not {solvers!r}")
+    m, n = A.shape
+    if tuple(B0.shape) != (n, m) or tuple(E.shape) != (n, m):
+        raise ValueError(f"B0 / E have shapes {tuple(B0.shape)} / {tuple(E.shape)}, expected ({n}, {m})")
+    b = np.asarray(b, dtype=np.float64).reshape(-1)
+    x_true = np.asarray(x_true, dtype=np.float64).reshape(-1)
+    if b.size != m or x_true.size != n:
+        raise ValueError(f"b / x_true have lengths {b.size} / {x_true.size}, expected {m} / {n}")
+    lam = {"ab": np.full(nl, np.nan), "ba": np.full(nl, np.nan)}
+    if lambdas is not None:
+        lab, lba = (np.asarray(v, dtype=np.float64).reshape(-1) for v in lambdas)
+        if lab.size != nl or lba.size != nl:
+            raise ValueError(f"lambdas: one value per mismatch level ({nl}) and side")
+        lam = {"ab": lab, "ba": lba}
+    out = {"c_range": cr, "mismatch_norms": np.abs(cr) * _fro(E)}          # :33-36
+    ctx = ctx or (A.ctx if isinstance(A, core.SparseOperator) else core.default_context())
+    Ao = core.as_operator(A, ctx)                              # uploaded once, reused by every solve
+    Bo = core.as_operator(B0, ctx)
+    Eo = core.as_operator(E, ctx)
+    chunks = [(lo, min(nl, lo + 64)) for lo in range(0, nl, 64)]            # at most 64 levels per call
+    if lambdas is None:                                        # :42-50
+        for side in sorted({keys[s][0] for s in solvers if keys[s][1]}):
+            trace_m = m if side == "ab" else n                 # gcv_function.m:46-50
+            for lo, hi in chunks:
+                H, beta, _ = core.arnoldi_mismatch(Ao, Bo, Eo, cr[lo:hi], b, k_gcv, side, ctx=ctx)
+                for i in range(lo, hi):
+                    lam[side][i] = core.gcv_fminbnd(H[i - lo], beta[i - lo], trace_m, 1e-9, 1e-1, 1e-8)[0]
+    out["lambda_gcv_ab"], out["lambda_gcv_ba"] = lam["ab"], lam["ba"]
+    for key in solvers:
+        side, hybrid = keys[key]
+        fin, nit = np.full(nl, np.nan), np.zeros(nl, dtype=int)
+        for lo, hi in chunks:
+            R = core.gmres_bounds_mismatch(Ao, Bo, Eo, cr[lo:hi], b, x_true, tol, maxit, side,
+                                           lambdas=lam[side][lo:hi] if hybrid else None, ctx=ctx)
+            ok = R.niters >= 1
+            fin[lo:hi][ok] = R.error_norm[R.niters[ok] - 1, np.nonzero(ok)[0]]     # err(end), :54 / :57
+            nit[lo:hi] = R.niters
+        out[f"final_errors_{key}"] = fin
+        out[f"niters_{key}"] = nit
+    return out

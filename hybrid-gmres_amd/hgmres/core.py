@@ -490,6 +490,60 @@ def spmm(A: "SparseOperator", X):
     return Y
 
 
+def _pert_pair(B0, E):
+    """The (B0, E) operator pair of a perturbed product, checked on the host."""
+    if not isinstance(B0, SparseOperator) or not isinstance(E, SparseOperator):
+        raise TypeError("B0 and E must be SparseOperators (hgmres.as_operator)")
+    if E.shape != B0.shape:
+        raise ValueError(f"E has shape {E.shape}, expected B0's {B0.shape}")
+    if B0.dtype != L.HGM_F64 or E.dtype != L.HGM_F64:
+        raise ValueError("perturbed product: fp64 operators only")
+
+
+def _coefs(coefs, lo, hi, what):
+    cf = np.ascontiguousarray(np.asarray(coefs, dtype=np.float64).reshape(-1))
+    if not lo <= cf.size <= hi:
+        raise ValueError(f"{what} takes {lo} to {hi} coefficients, not {cf.size}")
+    if not np.all(np.isfinite(cf)):
+        raise ValueError(f"{what}: every coefficient must be finite")
+    return cf
+
+
+def spmm_pert(B0: "SparseOperator", E: "SparseOperator", coefs, X):
+    """``B0 @ X[:, r] + coefs[r] * (E @ X[:, r])`` for an ``n x nvec`` host array ``X`` (``1 <= nvec <= 8``) through
+    ``hgm_spmm_pert``: column r is the product with ``B0 + coefs[r] * E``, which is never formed, and both
+    operators' entries are read once for all columns (spmm.hip).  ``E`` has ``B0``'s shape; when it also has its
+    sparsity pattern the index stream and the x gathers are shared.  A column's bits depend on its coefficient
+    only: not on ``nvec``, its position, the other columns or their coefficients."""
+    _pert_pair(B0, E)
+    m, n = B0.shape
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    if X.ndim != 2 or X.shape[0] != n:
+        raise ValueError(f"X has shape {X.shape}, expected ({n}, nvec)")
+    nv = X.shape[1]
+    if not 1 <= nv <= 8:
+        raise ValueError(f"spmm_pert takes 1 to 8 vectors, not {nv}")
+    cf = _coefs(coefs, nv, nv, f"spmm_pert of {nv} vectors")
+    ctx = B0.ctx
+    lib = L.load()
+    Xf = np.asfortranarray(X)
+    Y = np.empty((m, nv), order="F")
+    ptr = [C.c_void_p() for _ in range(2)]
+    try:
+        for p_, k in zip(ptr, (n * nv, m * nv)):
+            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, k), C.byref(p_)), ctx)
+        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
+        _check(lib.hgm_spmm_pert(ctx.handle, B0._h, E._h, nv, _dp(cf), ptr[0], max(n, 1), ptr[1], max(m, 1)), ctx)
+        _check(lib.hgm_memcpy_d2h(ctx.handle, Y.ctypes.data_as(C.c_void_p), ptr[1], 8 * m * nv), ctx)
+    finally:
+        for p_ in ptr:
+            if p_.value:
+                lib.hgm_dev_free(ctx.handle, p_)
+    return Y
+
+
 def fused_plan_info(A: "SparseOperator", B: "SparseOperator"):
     """The one-pass plan of (A, B) under the context's options (built if needed): dict with the
     build seconds, a checksum over every plan array, the partial slots and whether the device built
@@ -782,6 +836,85 @@ def gmres_bounds_batch(A, B, Bm, x_true, tol, maxit, side, *, lambdas=None, ctx=
         _check(rc, ctx)
     return BatchResult(X, err, res, nit.astype(int), st.astype(int),
                        H.reshape(nrhs, maxit, maxit + 1).transpose(0, 2, 1).copy() if return_H else None)
+
+
+def _mismatch_args(A, B0, E, coefs, b, what):
+    """Host-side checks shared by the mismatch bindings (before anything is uploaded): shapes and
+    coefficients.  Returns (m, n, coefs, b)."""
+    m, n = A.shape
+    if tuple(B0.shape) != (n, m):
+        raise ValueError(f"dimension mismatch: A is {tuple(A.shape)}, B0 is {tuple(B0.shape)} (expected size(A'))")
+    if tuple(E.shape) != (n, m):
+        raise ValueError(f"E has shape {tuple(E.shape)}, expected B0's ({n}, {m})")
+    cf = _coefs(coefs, 1, 64, what)
+    return m, n, cf, _f64(b, m, "b")
+
+
+def _mismatch_ops(A, B0, E, ctx):
+    ctx, Ao, Bo = _ops(A, B0, ctx)
+    return ctx, Ao, Bo, as_operator(E, ctx, Ao.dtype)
+
+
+def gmres_bounds_mismatch(A, B0, E, coefs, b, x_true, tol, maxit, side, *, lambdas=None, ctx=None, orth="mgs",
+                          return_H=False):
+    """``len(coefs)`` lockstep solves of one ``*_bounds`` solver of ONE ``b`` against back-projectors that
+    differ in a scalar (``hgm_gmres_bounds_mismatch``): column j of the returned :class:`BatchResult` is what
+    ``{AB,BA}gmres_{hybrid,nonhybrid}_bounds`` returns with ``B = B0 + coefs[j] * E`` and ``lambdas[j]`` -- the
+    loop over the mismatch levels of ``plot_error_vs_mismatch_norm.m:23-61``.  No ``B0 + c * E`` is formed or
+    uploaded: ``B0`` and ``E`` (``B0``'s shape; its sparsity pattern, or one of its own) are read once per
+    group of up to 8 running levels and iteration.  ``side`` is 'ab' or 'ba'; ``lambdas=None`` selects the
+    non-hybrid solver; ``x_true`` may be None (the error histories stay NaN).  At most 64 levels per call.
+    Per-column stopping and breakdown as :func:`gmres_bounds_batch`."""
+    sd = _side(side)
+    m, n, cf, b = _mismatch_args(A, B0, E, coefs, b, "gmres_bounds_mismatch")
+    nc = cf.size
+    maxit = int(maxit)
+    if maxit < 1:
+        raise ValueError("maxit must be >= 1")
+    lam = None
+    if lambdas is not None:
+        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+        if lam.size != nc:
+            raise ValueError(f"lambdas has {lam.size} entries, expected one per coefficient ({nc})")
+    xt = _f64(x_true, n, "x_true") if x_true is not None else None
+    ctx, Ao, Bo, Eo = _mismatch_ops(A, B0, E, ctx)
+    X = np.full((n, nc), np.nan, order="F")
+    err = np.full((maxit, nc), np.nan, order="F")
+    res = np.full((maxit, nc), np.nan, order="F")
+    nit = np.zeros(nc, dtype=np.int32)
+    st = np.zeros(nc, dtype=np.int32)
+    H = np.zeros((maxit + 1) * maxit * nc) if return_H else None
+    o = _opts(orth, H)
+    ip = C.POINTER(C.c_int)
+    rc = L.load().hgm_gmres_bounds_mismatch(ctx.handle, C.byref(o), Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), _dp(xt),
+                                            float(tol), maxit, _dp(lam), sd, 0 if lam is None else 1, _dp(X),
+                                            max(n, 1), _dp(err), _dp(res), nit.ctypes.data_as(ip),
+                                            st.ctypes.data_as(ip))
+    if rc != L.HGM_E_NOT_ASSIGNED:
+        _check(rc, ctx)
+    return BatchResult(X, err, res, nit.astype(int), st.astype(int),
+                       H.reshape(nc, maxit, maxit + 1).transpose(0, 2, 1).copy() if return_H else None)
+
+
+def arnoldi_mismatch(A, B0, E, coefs, b, k, gcv_type="ba", *, ctx=None, breakdown_tol=1e-12, orth="mgs"):
+    """:func:`arnoldi` with the back-projector ``B0 + coefs[j] * E`` for every j in lockstep
+    (``hgm_arnoldi_mismatch``; the GCV Arnoldis of ``plot_error_vs_mismatch_norm.m:46-50``): returns
+    (H, beta, kdone) with ``H`` of shape ``ncoef x (k+1) x k`` and ``beta``, ``kdone`` of length ``ncoef``."""
+    sd = _side(gcv_type)
+    m, n, cf, b = _mismatch_args(A, B0, E, coefs, b, "arnoldi_mismatch")
+    nc = cf.size
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    ctx, Ao, Bo, Eo = _mismatch_ops(A, B0, E, ctx)
+    H = np.zeros((k + 1) * k * nc)
+    beta = np.zeros(nc)
+    kd = np.zeros(nc, dtype=np.int32)
+    o = L.HGM_CGS2 if str(orth).lower() == "cgs2" else L.HGM_MGS
+    _check(L.load().hgm_arnoldi_mismatch(ctx.handle, Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), k, sd,
+                                         float(breakdown_tol), o, _dp(H), _dp(beta),
+                                         kd.ctypes.data_as(C.POINTER(C.c_int))), ctx)
+    return H.reshape(nc, k, k + 1).transpose(0, 2, 1).copy(), beta, kd.astype(int)
 
 
 def proj_norms(V, Y, t=None, *, ctx=None, loop=False):

@@ -23,6 +23,11 @@
  *                               over *_hybrid_bounds.m (one Arnoldi for every lambda)
  *   hgm_gmres_bounds_batch   <- the loop over the noise levels of plot_error_vs_noise_level.m:28-54 over the
  *                               four *_bounds.m (many right-hand sides, one operator pair)
+ *   hgm_gmres_bounds_mismatch <- the loop over the mismatch levels c of plot_error_vs_mismatch_norm.m:23-61 /
+ *                               run_2D_phantom.m:79-102 (B_pert = A' + c*E: one b, many back-projectors that
+ *                               differ in a scalar; no B_pert is formed)
+ *   hgm_arnoldi_mismatch     <- the GCV Arnoldis of that loop (plot_error_vs_mismatch_norm.m:46-50 over
+ *                               gcv_function.m:3-33), every level in lockstep
  *   hgm_gmres_bounds_filter  <- outputs 5-8 of the four *_bounds.m (phi/dphi filter-factor bounds,
  *                               eig(M) of :4-9 replaced by device Ritz pairs)
  *   hgm_mat_create_csc       <- MATLAB sparse (CSC, jc/ir/pr) operand hand-over
@@ -192,7 +197,11 @@ enum hgm_ctx_option {
     HGM_OPT_FUSED_VSDEPTH = 38     /* ... the compact pass of option 37 only: batches in ITS load ring, 2, 3 or
                                       4 [3] (every other pass keeps option 28's depth 2; the same bits at
                                       every depth; 3 is 1 % faster than 2 at C4).  The default
-                                      library carries 2 and 3; [experiments] 4 (measured slower) */
+                                      library carries 2 and 3; [experiments] 4 (measured slower) */,
+    HGM_OPT_PERT_SHARED = 39       /* perturbed product (hgm_spmm_pert, hgm_gmres_bounds_mismatch, hgm_arnoldi_mismatch):
+                                      when E has B0's sparsity pattern, one index stream and one x gather per
+                                      entry serve both value streams [1]; 0 forces the general two-pattern walk
+                                      (the same bits: a test and measurement hook) */
 };
 
 /* Host all-reduce hook (sum, in place, host memory) used instead of RCCL for
@@ -336,6 +345,17 @@ HGM_API int hgm_spmv_ab(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, const 
  * a column's bits do not depend on nvec, on its position, or on the other columns. */
 HGM_API int hgm_spmm(hgm_ctx*, const hgm_mat* A, int nvec, const double* X_dev, int64_t ldx,
                      double* Y_dev, int64_t ldy);
+/* Y(:,r) = B0*X(:,r) + coefs[r] * (E*X(:,r)), r < nvec, 1 <= nvec <= 8: the product with the perturbed
+ * operators B0 + coefs[r]*E, none of which is formed.  X, Y, ldx, ldy and the pixel order as hgm_spmm;
+ * coefs: nvec host values.  B0's and E's entries are read ONCE for all nvec vectors; when E has B0's
+ * sparsity pattern (compared on the device, once per call) one index stream and one x gather per entry
+ * serve both value streams (HGM_OPT_PERT_SHARED).  Y(:,r) is (B0*X(:,r)) + (coefs[r] * (E*X(:,r))) with
+ * two roundings: a column's bits depend on its coefficient only, not on nvec, its position, the other
+ * columns or their coefficients, and not on whether the pattern was shared.  HGM_E_ARG for fp32
+ * operators, a non-finite coefficient, and an E whose shape or stored row / column order (hgm_mat_order)
+ * differs from B0's. */
+HGM_API int hgm_spmm_pert(hgm_ctx*, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs_host,
+                          const double* X_dev, int64_t ldx, double* Y_dev, int64_t ldy);
 /* Multi-coefficient projected norms (the monitors of hgm_gmres_bounds_sweep), on device pointers:
  * V is rows x k column-major with leading dimension ldv >= rows, Y is k x nlam column-major (ldy >= k),
  * t has rows entries (NULL: zeros).  For every column l, in ONE pass over V (the rows x nlam product is
@@ -451,6 +471,21 @@ HGM_API int hgm_gmres_bounds_batch(hgm_ctx*, const hgm_opts*, const hgm_mat* A, 
         const double* Bm, int64_t ldb, int nrhs, const double* x_true, int64_t ldxt, double tol, int maxit,
         const double* lambdas, int side, int hybrid, double* X, int64_t ldx,
         double* error_hist, double* residual_hist, int* niters, int* col_status);
+/* ncoef lockstep solves of one *_bounds solver (side, hybrid) of ONE right-hand side b (m) and one x_true
+ * (n, may be NULL) against back-projectors that differ in a scalar: column j of every output is what
+ * hgm_gmres_bounds_ex returns with B = B0 + coefs[j]*E and lambda = lambdas[j].  (The loop over the
+ * mismatch levels of plot_error_vs_mismatch_norm.m:23-61.)  No B0 + c*E is formed: per iteration B0's and
+ * E's entries are read once per group of up to 8 running levels, hgm_spmm_pert's kernel; the A pass is
+ * hgm_spmm's.  lambdas: ncoef entries, required with hybrid = 1.  Output layout, NaN padding, per-column
+ * stopping, breakdown and col_status conventions, and opts (orth; H_out receives ncoef Hessenbergs) are
+ * hgm_gmres_bounds_batch's.  1 <= ncoef <= 64.  Refused: HGM_E_ARG for fp32 operators, parity mode,
+ * HGM_DEVICE_PTRS, ncoef out of range, a non-finite coefficient, with hybrid = 1 a negative or non-finite
+ * lambda, and an E whose shape or stored row / column order (hgm_mat_order) differs from B0's;
+ * HGM_E_UNSUPPORTED on a communicator or a context with a host all-reduce hook. */
+HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx*, const hgm_opts*, const hgm_mat* A, const hgm_mat* B0,
+        const hgm_mat* E, const double* coefs, int ncoef, const double* b, const double* x_true, double tol,
+        int maxit, const double* lambdas, int side, int hybrid, double* X, int64_t ldx,
+        double* error_hist, double* residual_hist, int* niters, int* col_status);
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* ctx, const hgm_opts* opts, const hgm_mat* A,
                                const hgm_mat* At, const double* b, const double* x_true, double tol,
                                int maxit, double* x, double* error_norm, double* residual_norm,
@@ -466,6 +501,12 @@ HGM_API int hgm_lsmr_solver_ex(hgm_ctx* ctx, const hgm_opts* opts, const hgm_mat
 HGM_API int hgm_arnoldi(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, const double* b,
                         int k, int side, double breakdown_tol, int orth, double* H,
                         double* beta, int* kdone);
+/* hgm_arnoldi with the back-projector B0 + coefs[j]*E for every j < ncoef in lockstep (operator passes and
+ * refusals as hgm_gmres_bounds_mismatch): H holds ncoef consecutive (k+1) x k blocks, beta[ncoef] and
+ * kdone[ncoef] follow hgm_arnoldi's break convention per column. */
+HGM_API int hgm_arnoldi_mismatch(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
+                                 const double* coefs, int ncoef, const double* b, int k, int side,
+                                 double breakdown_tol, int orth, double* H, double* beta, int* kdone);
 /* λ-dependent part of gcv_function.m:35-58 on a cached H (host only). */
 HGM_API int hgm_gcv_from_H(const double* H, int k, double beta, double lambda, double trace_m,
                            double* gcv_val);
@@ -512,7 +553,8 @@ HGM_API int hgm_eig(int n, const double* A, double* wr, double* wi, double* V);
  * last reset, measured with HIP events on the context stream.  classes:
  * 0 = SpMV on A (ray-major), 1 = SpMV on B/Aᵀ (pixel-major), 2 = MGS pass, 3 = the one-pass A*(B*q),
  * 4 = the launches of a hgm_proj_norms / hgm_proj_norms_loop call, 5 = the launches of an hgm_spmm
- * product, pack/unpack included (and each operator pass group of hgm_gmres_bounds_batch).
+ * or hgm_spmm_pert product, pack/unpack included (and each operator pass group of hgm_gmres_bounds_batch,
+ * hgm_gmres_bounds_mismatch and hgm_arnoldi_mismatch).
  * enable: 0 = off, 1 = every class, HGM_TIMING_CLASSES(mask) = only the classes whose
  * bit is set (each timed launch carries events, so time only what is read). */
 #define HGM_TIMING_CLASSES(mask) (0x100 | (mask))

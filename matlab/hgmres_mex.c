@@ -29,6 +29,11 @@
  *        batch (hgm_gmres_bounds_batch): column j is the solve of Bm(:,j) with lambdas(j); x_true is n x 1 (shared),
  *        n x nrhs or []; maxit x nrhs histories (NaN past niters(j)); status(j) ~= 0 marks a column whose x was never
  *        assigned (its X column is NaN).  Always the production kernels (the batch has no parity form).
+ *   hgmres_mex('gmres_bounds_mismatch', side,hybrid, A,B0,E,coefs,b,x_true,tol,maxit[,lambdas])
+ *        -> [X, error_hist, residual_hist, niters, status]   the loop over the mismatch levels of
+ *        plot_error_vs_mismatch_norm.m:23-61 over one {AB,BA}gmres_{hybrid,nonhybrid}_bounds solver as ONE lockstep
+ *        sweep (hgm_gmres_bounds_mismatch): column j is the solve of b with B = B0 + coefs(j)*E and lambdas(j); no
+ *        B0 + c*E is formed.  x_true is n x 1 or []; outputs as 'gmres_bounds_batch'.  Always the production kernels.
  *   hgmres_mex('device', d)                      select the HIP device (default 0)
  *   hgmres_mex('parity', 'auto'|'on'|'off')      summation orders (below; default 'auto')
  *
@@ -527,6 +532,70 @@ static void bounds_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prh
     if (nlhs > 4) plhs[4] = cs;
 }
 
+/* [X, error_hist, residual_hist, niters, status] = hgmres_mex('gmres_bounds_mismatch', side, hybrid, A, B0, E, coefs,
+ * b, x_true, tol, maxit [, lambdas]).  Side, hybrid, every size, the coefficients and the lambdas are checked
+ * before a device is touched. */
+static void bounds_mismatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    const int side = side_of(prhs[1]);
+    const int hybrid = scalar(prhs[2], "hybrid") != 0.0;
+    need_double(prhs[3], "A");
+    need_double(prhs[4], "B0");
+    need_double(prhs[5], "E");
+    const int64_t m = (int64_t)mxGetM(prhs[3]), n = (int64_t)mxGetN(prhs[3]);
+    if ((int64_t)mxGetM(prhs[4]) != n || (int64_t)mxGetN(prhs[4]) != m)
+        fail("hgmres:arg", "hgmres: B0 must be size(A')");
+    if ((int64_t)mxGetM(prhs[5]) != n || (int64_t)mxGetN(prhs[5]) != m)
+        fail("hgmres:arg", "hgmres: E must be size(B0)");
+    need_double(prhs[6], "coefs");
+    const int64_t nc = (int64_t)mxGetNumberOfElements(prhs[6]);
+    if (mxIsSparse(prhs[6]) || nc < 1 || nc > 64)
+        fail("hgmres:arg", "hgmres: coefs must be a dense vector of 1 to 64 mismatch levels");
+    const double* cf = mxGetDoubles(prhs[6]);
+    for (int64_t j = 0; j < nc; ++j)
+        if (!isfinite(cf[j])) fail("hgmres:arg", "hgmres: every coefficient must be finite");
+    const double* b = vec(prhs[7], m, "b", 0);
+    const double* xt = vec(prhs[8], n, "x_true", 1);
+    const double tol = scalar(prhs[9], "tol");
+    const int maxit = maxit_of(prhs[10]);
+    const double* lam = NULL;
+    if (hybrid) {
+        if (nrhs < 12) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per mismatch level)");
+        need_double(prhs[11], "lambdas");
+        if (mxIsSparse(prhs[11]) || (int64_t)mxGetNumberOfElements(prhs[11]) != nc)
+            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per mismatch level");
+        lam = mxGetDoubles(prhs[11]);
+        for (int64_t j = 0; j < nc; ++j)
+            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
+    }
+    hgm_mat* A = op(prhs[3], "A");
+    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
+    hgm_mat* B0 = op(prhs[4], "B0");
+    hgm_mat* E = op(prhs[5], "E");
+    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nc, mxREAL);
+    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
+    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
+    int* nit = (int*)mxCalloc((size_t)nc, sizeof(int));
+    int* cst = (int*)mxCalloc((size_t)nc, sizeof(int));
+    for (int64_t i = 0; i < n * nc; ++i) mxGetDoubles(X)[i] = (double)NAN;
+    const int st = hgm_gmres_bounds_mismatch(ctx(), NULL, A, B0, E, cf, (int)nc, b, xt, tol, maxit, lam, side, hybrid,
+                                             mxGetDoubles(X), n > 0 ? n : 1, mxGetDoubles(e), mxGetDoubles(r), nit,
+                                             cst);
+    if (st != HGM_E_NOT_ASSIGNED) check(st);             /* unassigned columns are reported in status */
+    mxArray* ni = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
+    mxArray* cs = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
+    for (int64_t j = 0; j < nc; ++j) {
+        mxGetDoubles(ni)[j] = (double)nit[j];
+        mxGetDoubles(cs)[j] = (double)cst[j];
+    }
+    mxFree(nit);
+    mxFree(cst);
+    plhs[0] = X;
+    if (nlhs > 1) plhs[1] = e;
+    if (nlhs > 2) plhs[2] = r;
+    if (nlhs > 3) plhs[3] = ni;
+    if (nlhs > 4) plhs[4] = cs;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char fn[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], fn, sizeof fn) != 0)
@@ -561,6 +630,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(fn, "gmres_bounds_batch")) {
         nargs(nrhs, 8, 9, fn);
         bounds_batch(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(fn, "gmres_bounds_mismatch")) {
+        nargs(nrhs, 10, 11, fn);
+        bounds_mismatch(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(fn, "gmres_lambda_sweep")) {
         nargs(nrhs, 8, 8, fn);
         lambda_sweep(nlhs, plhs, prhs);
