@@ -1098,6 +1098,52 @@ HGM_API int hgm_spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int n
     return HGM_OK;
 }
 
+// hgm_spmm's hand-over around the interleaved linear-combination kernel (gkmv.hip)
+static void mv_axpby_norms_impl(hgm_ctx* c, int64_t n, int nvec, const double* a, const double* X, int64_t ldx,
+                                const double* b, const double* Y, int64_t ldy, double* Out, int64_t ldo, double* sumsq) {
+    HGM_HIP(hipSetDevice(c->device));
+    HGM_REQUIRE(n >= 0, "mv_axpby_norms: n >= 0");
+    HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, "mv_axpby_norms: 1 <= nvec <= 8");
+    HGM_REQUIRE(ldx >= n && ldy >= n && ldo >= n, "mv_axpby_norms: every leading dimension >= n");
+    const int NV = spmm_width(nvec);
+    double* Xi = c->buf<double>("gkmv_xi", (size_t)(n > 0 ? n : 1) * NV);
+    double* Yi = c->buf<double>("gkmv_yi", (size_t)(n > 0 ? n : 1) * NV);
+    double* sums = c->buf<double>("gkmv_sums", SPMM_MAXV);
+    MvCols sx, sy, so;
+    MvLin L;
+    for (int r = 0; r < SPMM_MAXV; ++r) {
+        sx.p[r] = r < nvec ? const_cast<double*>(X) + r * ldx : nullptr;
+        sy.p[r] = r < nvec ? const_cast<double*>(Y) + r * ldy : nullptr;
+        so.p[r] = r < nvec ? Out + r * ldo : nullptr;
+        L.a.c[r] = r < nvec ? a[r] : 0.0;
+        L.b.c[r] = r < nvec ? b[r] : 0.0;
+    }
+    L.X = Xi;
+    L.Y = Yi;
+    L.Out = Xi;
+    L.sum = sumsq ? MVS_SQ : MVS_NONE;
+    L.sums = sums;
+    hipEvent_t tm;
+    timing_begin(c, KC_GKMV, &tm);
+    mv_pack(c, n, nvec, sx, Xi);
+    mv_pack(c, n, nvec, sy, Yi);
+    mv_lin(c, n, nvec, L);
+    mv_unpack(c, n, nvec, Xi, so);
+    timing_end(c, KC_GKMV, tm, 8.0 * (double)n * (3.0 * nvec + 5.0 * NV));
+    if (sumsq) {
+        Reader rd(c);
+        rd.add(sumsq, sums, sizeof(double) * nvec);
+        rd.go();
+    }
+}
+
+HGM_API int hgm_mv_axpby_norms(hgm_ctx* c, int64_t n, int nvec, const double* a, const double* X, int64_t ldx,
+                               const double* b, const double* Y, int64_t ldy, double* Out, int64_t ldo, double* sumsq) {
+    if (!c || !a || !X || !b || !Y || !Out) return HGM_E_ARG;
+    HGM_TRY(c, mv_axpby_norms_impl(c, n, nvec, a, X, ldx, b, Y, ldy, Out, ldo, sumsq));
+    return HGM_OK;
+}
+
 HGM_API int hgm_proj_norms(hgm_ctx* c, int64_t rows, int k, const double* V, int64_t ldv, const double* Y,
                            int64_t ldy, int nlam, const double* t, double* sumsq_diff, double* sumsq) {
     if (!c || !V || !Y || !sumsq_diff) return HGM_E_ARG;
@@ -1249,6 +1295,13 @@ HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_m
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
     HGM_SOLVE(c, gmres_bounds_mismatch(c, o, A, B0, E, coefs, ncoef, b, xt, tol, maxit, lambdas, side, hybrid ? 1 : 0,
                                        X, ldx, err, res, niters, col_status));
+}
+HGM_API int hgm_gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
+                         int nrhs, const double* xt, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
+                         int hybrid, double* X, int64_t ldx, double* err, double* res, double* ar, int* niters) {
+    if (kind != HGM_GK_LSQR && kind != HGM_GK_LSMR) return HGM_E_ARG;
+    HGM_SOLVE(c, gk_batch(c, o, A, At, Bm, ldb, nrhs, xt, ldxt, tol, maxit, lambdas, kind, hybrid ? 1 : 0, X, ldx, err,
+                          res, ar, niters));
 }
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* b,
                                const double* xt, double tol, int maxit, double* x, double* err, double* res,

@@ -204,6 +204,26 @@ void proj_ls(const double* H, int ldh, int k, double beta, double* y) {
     qr_ls(k + 1, k, M.data(), rhs.data(), y);
 }
 
+void proj_hybrid_lsmr(const double* Bk, int ldb, int k, double alpha_next, double beta_k, double beta1, double lambda,
+                      double* y) {
+    std::vector<double> Gm((size_t)k * k, 0.0), G2((size_t)k * k, 0.0), RHS(k, 0.0);
+    normal_matrix(Bk, ldb, k, Gm.data());                                      // Bk'*Bk
+    for (int i = 0; i < k; ++i)
+        for (int j = 0; j < k; ++j) {
+            double s = 0;
+            for (int l = 0; l < k; ++l) s += Gm[(size_t)l * k + i] * Gm[(size_t)j * k + l];
+            G2[(size_t)j * k + i] = s;
+        }
+    const double ab = alpha_next * beta_k;
+    std::vector<double> LHS = G2;
+    LHS[0] += ab * ab;
+    for (int i = 0; i < k; ++i) LHS[(size_t)i * k + i] += lambda;
+    const double sc = Bk[0] * beta1;
+    for (int i = 0; i < k; ++i) RHS[i] = sc * Gm[i];
+    for (int i = 0; i < k; ++i) y[i] = 0.0;
+    mldivide_square(k, LHS.data(), RHS.data(), y);                             // :44
+}
+
 void proj_gram(const double* G, int ldg, const double* c, int k, double lambda, double* y) {
     std::vector<double> M((size_t)k * k);
     for (int j = 0; j < k; ++j)

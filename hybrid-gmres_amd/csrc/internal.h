@@ -61,14 +61,14 @@ struct DevBuf {
 };
 
 // Kernel classes timed by hgm_kernel_timing (bench roofline).
-enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_SPMM = 5, KC_N = 6 };
+enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_SPMM = 5, KC_GKMV = 6, KC_N = 7 };
 
 struct Timing {
     bool on = false;
     bool paused = false;   // hgm_kernel_timing_pause: armed but not recording
     unsigned mask = 0xffu;   // timed classes
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[KC_N];
-    double bytes[KC_N] = {0, 0, 0, 0, 0, 0};
+    double bytes[KC_N] = {0, 0, 0, 0, 0, 0, 0};
     std::vector<hipEvent_t> pool;
     hipEvent_t get();
     void clear();
@@ -383,6 +383,44 @@ void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi);
 bool same_pattern(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E);
 void spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, bool shared, int nvec, const double* coefs,
                const double* Xi, double* Yi);
+
+// Golub-Kahan recurrences on interleaved multi-vectors (gkmv.hip; hgm_mv_axpby_norms and the vector
+// kernels of hgm_gk_batch).  Per-slot coefficients travel by value; a slot's elements and sums depend on
+// its own data and the length only (not on nvec, the slot or the other slots).  Sums are written to
+// `sums` (spmm_width(nvec) device doubles, one per slot) in a fixed order with no atomics.
+struct MvCoef {
+    double c[SPMM_MAXV];
+};
+// per-slot sums of a launch: none, sum Out^2, sum (Out - D)^2 with D interleaved / one shared vector
+enum MvSum { MVS_NONE = 0, MVS_SQ = 1, MVS_DIFF = 2, MVS_DIFF_SHARED = 3 };
+// Out(i,r) = (a_r X(i,r)) [+ (b_r Y(i,r)) [+ (c_r Z(i,r))]], products and sums rounded one by one, left
+// to right; Out == nullptr: the sums alone; Out may alias an input
+struct MvLin {
+    int nterms = 2;
+    const double *X = nullptr, *Y = nullptr, *Z = nullptr;
+    MvCoef a{}, b{}, c{};
+    double* Out = nullptr;
+    int sum = MVS_NONE;
+    const double* D = nullptr;
+    double* sums = nullptr;
+};
+// new slot r = element stride[r] * i of p[r] (one slot of an old group of width stride[r]); nullptr: zeros
+struct MvSlots {
+    const double* p[SPMM_MAXV];
+    int stride[SPMM_MAXV];
+};
+int gkmv_grid(int64_t n);   // blocks of every gkmv launch (and partials per slot): from the length alone
+void mv_lin(hgm_ctx* c, int64_t n, int nvec, const MvLin& L);
+// Out = In / s_r (a true division); guard: only where s_r > 0
+void mv_div(hgm_ctx* c, int64_t n, int nvec, const double* In, double* Out, const MvCoef& s, bool guard);
+// lsqr_solver.m:28, :40-41 (+ the terms of :43): v = v / alpha, x = x + (cx w), w = v - (cw w)
+void mv_lsqr_step(hgm_ctx* c, int64_t n, int nvec, double* V, double* X, double* W, const MvCoef& alpha,
+                  const MvCoef& cx, const MvCoef& cw, int sum, const double* D, double* sums);
+// lsmr_solver.m:40, :61-67 (+ the terms of :72); first: :62 in place of :64
+void mv_lsmr_step(hgm_ctx* c, int64_t n, int nvec, double* V, double* X, double* H, double* HB, const MvCoef& alpha,
+                  const MvCoef& chb, const MvCoef& cx, const MvCoef& ch, bool first, int sum, const double* D,
+                  double* sums);
+void mv_regather(hgm_ctx* c, int64_t n, int nvec, const MvSlots& src, double* Out);
 
 // MGS sweep of v = Q(:,kk+1) against Q(:,0..kk); writes Hcol[0..kk+1] (device) and
 // normalises Q(:,kk+1) unless H(kk+1,kk) == 0.  dist: n-vectors sharded (scalar all-reduce
@@ -784,6 +822,9 @@ int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const
 int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs,
                      int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
                      double* beta_out, int* kdone);
+int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
+             int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
+             int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, double* ar_hist, int* niters);
 int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* b,
                         const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
                         const hgm_mat* dML, const hgm_mat* dMR, int ritz_steps, double* x_out, double* err_out,
@@ -808,6 +849,10 @@ void proj_ls(const double* H, int ldh, int k, double beta, double* y);
 // yk = (AQk'*AQk + lambda*eye(k)) \ (AQk'*b)   (hybrid_ab_gmres_rtp.m:32): G's columns (ldg apart) hold
 // the upper triangle of AQk'*AQk, c = AQk'*b
 void proj_gram(const double* G, int ldg, const double* c, int k, double lambda, double* y);
+// hybrid_lsmr_solver.m:37-44 on the lower-bidiagonal Bk ((k+1) x k leading part, leading dimension ldb):
+// y = ((Bk'*Bk)^2 + (alpha_next*beta_k)^2 e1 e1' + lambda*eye(k)) \ (Bk(1,1)*beta1 * (Bk'*Bk) e1)
+void proj_hybrid_lsmr(const double* Bk, int ldb, int k, double alpha_next, double beta_k, double beta1, double lambda,
+                      double* y);
 double gcv_from_H(const double* H, int ldh, int k, double beta, double lambda, double trace_m);
 // MATLAB fminbnd (Brent / Forsythe-Malcolm-Moler fmin) of gcv_from_H over [lo, hi].
 double gcv_fminbnd(const double* H, int k, double beta, double trace_m, double lo, double hi,

@@ -1478,7 +1478,7 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
     double alpha1 = std::sqrt(read1<double>(c, sl + S_ALPHA));                      // :14
     div_scalar<double>(c, n, v0, v0, alpha1);                                       // :15-16
     int k = 0;
-    std::vector<double> Gm, G2, LHS, RHS, y;
+    std::vector<double> y;
     for (k = 0; k < maxit; ++k) {
         double* vk = V + (int64_t)k * ldv;
         BK(k, k) = alpha1;                                                     // :23
@@ -1497,24 +1497,8 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
         }
         const int kk = k + 1;
         // :37-44  LHS = (Bk'*Bk)^2 + (alpha_k1*beta_k1)^2 e1 e1' + lambda I ; RHS = B_k(1,1) beta1 (Bk'*Bk) e1
-        Gm.assign((size_t)kk * kk, 0.0);
-        dense::normal_matrix(Bk.data(), maxit + 1, kk, Gm.data());                 // Bk'*Bk
-        G2.assign((size_t)kk * kk, 0.0);
-        for (int i = 0; i < kk; ++i)
-            for (int j = 0; j < kk; ++j) {
-                double s = 0;
-                for (int l = 0; l < kk; ++l) s += Gm[(size_t)l * kk + i] * Gm[(size_t)j * kk + l];
-                G2[(size_t)j * kk + i] = s;
-            }
-        const double ab = alpha1 * beta_k;
-        LHS = G2;
-        LHS[0] += ab * ab;
-        for (int i = 0; i < kk; ++i) LHS[(size_t)i * kk + i] += lambda;
-        RHS.assign(kk, 0.0);
-        const double sc = BK(0, 0) * beta1;
-        for (int i = 0; i < kk; ++i) RHS[i] = sc * Gm[i];
         y.assign(kk, 0.0);
-        dense::mldivide_square(kk, LHS.data(), RHS.data(), y.data());          // :44
+        dense::proj_hybrid_lsmr(Bk.data(), maxit + 1, kk, alpha1, beta_k, beta1, lambda, y.data());   // :44
         h2d_pinned(c, yd, y.data(), sizeof(double) * kk);
         gemv<double>(c, n, kk, V, ldv, yd, x, 0);                                   // :45
         nsumsq_diff<double>(c, n, x, xt, sl + S_ERR);                               // :47
@@ -2144,6 +2128,464 @@ int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_
                                  nullptr, nullptr, done.data(), nullptr);
     if (kdone) std::copy(done.begin(), done.end(), kdone);
     return st;
+}
+
+// ============================================================================
+// Lockstep Golub-Kahan solves (hgm_gk_batch)
+// ============================================================================
+// lsqr_solver.m, hybrid_lsqr_solver.m, lsmr_solver.m or hybrid_lsmr_solver.m for nrhs columns
+// (b_j, x_true_j, lambda_j) in lockstep.  Every state vector (u, v, x, w / h, hbar, the hybrid's lower
+// block u_n, and b and x_true themselves) lives in spmm.hip's interleaved layout for the whole solve, in
+// groups of up to 8 running columns: spmm(A) and spmm(At) read each operator once per group and pass,
+// straight on that state, and the recurrences are gkmv.hip's per-slot kernels.  Packs and unpacks happen
+// only at entry, when a column leaves (its x), and for hybrid LSMR's basis column and x = V_k y.  The
+// scalars (beta^2, alpha^2, the monitors) of all running columns come back in one transfer each, at
+// most three per iteration; the rotations (lsqr_rotate / lsmr_rotate) and the projected solve of hybrid
+// LSMR run on the host per column.  A column that stops has its x extracted at that iteration; when the
+// running columns then fit narrower groups they are re-gathered (mv_regather).  No kernel's result for
+// a slot depends on the group's width, the slot or the other slots, so a column's bits do not depend
+// on its neighbours.
+namespace {
+// one interleaved state vector of the batch: group g at p + g * max(len, 1) * SPMM_MAXV
+struct GkVec {
+    double* p = nullptr;
+    int64_t len = 0;
+    double* at(size_t g) const { return p + g * (size_t)(len > 0 ? len : 1) * SPMM_MAXV; }
+};
+}  // namespace
+
+int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
+             int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
+             int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, double* ar_hist, int* niters) {
+    const std::string what = "Golub-Kahan batch";
+    lockstep_guard(c, o, A, At, what);
+    HGM_REQUIRE(kind == HGM_GK_LSQR || kind == HGM_GK_LSMR, what + ": kind is HGM_GK_LSQR or HGM_GK_LSMR");
+    HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, what + ": 1 <= nrhs <= 64");
+    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+    HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
+    const int64_t m = A->rows, n = A->cols;
+    HGM_REQUIRE(ldb == 0 || ldb >= m, what + ": ldb is 0 (one shared b) or >= rows(A)");
+    HGM_REQUIRE(X_out == nullptr || ldx >= n, what + ": ldx >= cols(A)");
+    HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, what + ": ldxt is 0 (one shared x_true) or >= cols(A)");
+    lockstep_lambdas(lambdas, nrhs, hybrid, what);
+    const PixOrder po = n_order(c, A, At);
+    const bool lsmr = kind == HGM_GK_LSMR, hyb = hybrid != 0;
+    const bool hlsqr = !lsmr && hyb, plsmr = lsmr && !hyb, hlsmr = lsmr && hyb;
+    const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (err_hist) std::fill(err_hist, err_hist + (size_t)maxit * nrhs, nan);
+    if (res_hist) std::fill(res_hist, res_hist + (size_t)maxit * nrhs, nan);
+    if (ar_hist) std::fill(ar_hist, ar_hist + (size_t)maxit * nrhs, nan);
+    for (int j = 0; j < nrhs; ++j) niters[j] = 0;
+
+    // ---- device storage ----
+    const size_t G0 = (size_t)(nrhs + SPMM_MAXV - 1) / SPMM_MAXV;
+    auto vec = [&](const char* name, int64_t len) {
+        GkVec v;
+        v.len = len;
+        v.p = c->buf<double>(name, G0 * (size_t)(len > 0 ? len : 1) * SPMM_MAXV);
+        return v;
+    };
+    const bool xt_cols = xt_in && ldxt != 0;                 // else one x_true shared by every column (or none)
+    GkVec U = vec("gk_u", m), Bi = vec("gk_b", m), V = vec("gk_v", n), X = vec("gk_x", n);
+    GkVec W, H, HB, UN, XT;
+    if (!lsmr) W = vec("gk_w", n);
+    if (plsmr) {
+        H = vec("gk_h", n);
+        HB = vec("gk_hbar", n);
+    }
+    if (hlsqr) UN = vec("gk_un", n);                         // lower block of u_aug (hybrid_lsqr_solver.m:6)
+    if (xt_cols) XT = vec("gk_xt", n);
+    GkVec tmp_m = vec("gk_tmp_m", m), tmp_n = vec("gk_tmp_n", n);   // re-gather targets
+    double* Tm = c->buf<double>("gk_tm", (size_t)(m > 0 ? m : 1) * SPMM_MAXV);   // one group's product
+    double* Tn = c->buf<double>("gk_tn", (size_t)(n > 0 ? n : 1) * SPMM_MAXV);
+    const int nb_cols = ldb == 0 ? 1 : nrhs;
+    const int nxt_cols = xt_cols ? nrhs : 1;
+    double* ball = c->buf<double>("gk_ball", (size_t)ldm * nb_cols);
+    double* xtall = c->buf<double>("gk_xtall", (size_t)ldn * nxt_cols);
+    double* xall = c->buf<double>("gk_xall", (size_t)ldn * nrhs);
+    double* dump = c->buf<double>("gk_dump", (size_t)ldn);   // where the slots of finished columns unpack to
+    double* Vall = hlsmr ? c->buf<double>("gk_V", (size_t)ldn * maxit * nrhs) : nullptr;   // per-column bases V_j
+    double* Yd = hlsmr ? c->buf<double>("gk_y", (size_t)maxit * nrhs) : nullptr;
+    double* dsum = c->buf<double>("gk_sums", 3 * G0 * SPMM_MAXV);
+    std::vector<double> hsum(3 * G0 * SPMM_MAXV, 0.0);
+    auto ds = [&](int q, size_t g) { return dsum + ((size_t)q * G0 + g) * SPMM_MAXV; };
+    auto hs = [&](int q, size_t g, size_t r) { return hsum[((size_t)q * G0 + g) * SPMM_MAXV + r]; };
+    auto readback = [&](int nq) {                            // the sums of every running column, one transfer
+        Reader rd(c);
+        rd.add(hsum.data(), dsum, sizeof(double) * (size_t)nq * G0 * SPMM_MAXV);
+        rd.go();
+    };
+    auto bj = [&](int j) { return ball + (size_t)ldm * (nb_cols == 1 ? 0 : j); };
+    auto xtj = [&](int j) { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
+    auto xj = [&](int j) { return xall + (size_t)ldn * j; };
+    auto Vj = [&](int j) { return Vall + (size_t)ldn * maxit * j; };
+
+    for (int j = 0; j < nb_cols; ++j) h2d(c, bj(j), Bm + (size_t)ldb * j, sizeof(double) * m);
+    if (xt_in) {
+        // x_true in the reference order, permuted into the operators' stored pixel order
+        double* tmp = po.trivial() ? nullptr : c->buf<double>("gk_xt_ref", n > 0 ? n : 1);
+        for (int j = 0; j < nxt_cols; ++j) {
+            h2d(c, po.trivial() ? xtj(j) : tmp, xt_in + (size_t)ldxt * j, sizeof(double) * n);
+            if (!po.trivial()) pix_permute<double>(c, po, tmp, xtj(j), 0);
+        }
+    }
+    const int errmode = !xt_in ? MVS_NONE : xt_cols ? MVS_DIFF : MVS_DIFF_SHARED;
+
+    // ---- the running columns, in groups of at most 8: slot -> column, -1 once the column has left ----
+    std::vector<std::vector<int>> groups(G0);
+    for (int j = 0; j < nrhs; ++j) groups[j / SPMM_MAXV].push_back(j);
+    auto ptrs = [&](const std::vector<int>& g, auto colptr, double* dead) {
+        MvCols t;
+        for (size_t r = 0; r < (size_t)SPMM_MAXV; ++r)
+            t.p[r] = r < g.size() ? (g[r] >= 0 ? colptr(g[r]) : dead) : nullptr;
+        return t;
+    };
+    auto coef = [&](const std::vector<int>& g, double dead, auto f) {
+        MvCoef k;
+        for (size_t r = 0; r < (size_t)SPMM_MAXV; ++r) k.c[r] = r < g.size() && g[r] >= 0 ? (double)f(g[r]) : dead;
+        return k;
+    };
+    auto product = [&](const hgm_mat* M, int nv, const double* in, double* out) {
+        hipEvent_t tev = nullptr;
+        timing_begin(c, KC_SPMM, &tev);
+        spmm(c, M, nv, in, out);
+        timing_end(c, KC_SPMM, tev, 12.0 * M->nnz + 8.0 * spmm_width(nv) * (M->rows + M->cols));
+    };
+    // a launch (or a few) of the interleaved vector kernels over nvecs multi-vectors of length len
+    auto vk = [&](int64_t len, int nv, int nvecs, auto&& fn) {
+        hipEvent_t tev = nullptr;
+        timing_begin(c, KC_GKMV, &tev);
+        fn();
+        timing_end(c, KC_GKMV, tev, 8.0 * spmm_width(nv) * (double)len * nvecs);
+    };
+    // Out = (a X) + (b Y) [+ (cz Z)] over one group, with per-slot sums of squares into sums
+    auto lin = [&](int64_t len, int nv, int nterms, const double* Xp, const MvCoef& a, const double* Yp,
+                   const MvCoef& b, const double* Zp, const MvCoef& cz, double* Out, int sum, const double* D,
+                   double* sums) {
+        MvLin L;
+        L.nterms = nterms;
+        L.X = Xp;
+        L.Y = Yp;
+        L.Z = Zp;
+        L.a = a;
+        L.b = b;
+        L.c = cz;
+        L.Out = Out;
+        L.sum = sum;
+        L.D = D;
+        L.sums = sums;
+        vk(len, nv, nterms + (Out ? 1 : 0) + (sum == MVS_DIFF ? 1 : 0), [&] { mv_lin(c, len, nv, L); });
+    };
+    const double* xt_shared = errmode == MVS_DIFF_SHARED ? xtall : nullptr;
+    auto errD = [&](size_t g) -> const double* { return errmode == MVS_DIFF ? XT.at(g) : xt_shared; };
+    auto copy_group = [&](double* dst, const double* src, int64_t len, int nv) {
+        if (len > 0)
+            HGM_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)len * spmm_width(nv), hipMemcpyDeviceToDevice,
+                                   c->stream));
+    };
+    auto zero_group = [&](double* dst, int64_t len, int nv) {
+        if (len > 0) HGM_HIP(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)len * spmm_width(nv), c->stream));
+    };
+    MvCoef ones, minus1, none{};
+    for (int r = 0; r < SPMM_MAXV; ++r) {
+        ones.c[r] = 1.0;
+        minus1.c[r] = -1.0;
+    }
+
+    // ---- per-column scalars (host, double) ----
+    std::vector<double> nb(nrhs), nxt(nrhs, 0.0), beta(nrhs), alpha(nrhs), sq(nrhs, 0.0);
+    std::vector<double> rho_bar(nrhs), phi_bar(nrhs), c_x(nrhs, 0.0), c_w(nrhs, 0.0);       // LSQR
+    std::vector<double> rot((size_t)9 * nrhs, 0.0), cf((size_t)3 * nrhs, 0.0);              // LSMR (lsmr_rotate)
+    const size_t bks = (size_t)(maxit + 1) * maxit;
+    std::vector<double> Bk(hlsmr ? bks * nrhs : 0, 0.0), Yh(hlsmr ? (size_t)maxit * nrhs : 0, 0.0);   // hybrid LSMR :11
+    std::vector<double> beta1(nrhs, 0.0);
+    std::vector<char> stop(nrhs, 0);
+    if (hyb)
+        for (int j = 0; j < nrhs; ++j) sq[j] = std::sqrt(lambdas[j]);
+    double normA = A->fro;                                    // ||A||_F (lsmr_solver.m:71), cached per operator
+    if (plsmr && A->fro < 0) {
+        double* f = reinterpret_cast<double*>(c->dscal) + 64;
+        fro2<double>(c, A, f);
+        normA = std::sqrt(read1<double>(c, f));
+        const_cast<hgm_mat*>(A)->fro = normA;
+    }
+
+    // ---- start: ||b||, ||x_true||, u = b / beta, v = A'u / alpha ----
+    if (errmode == MVS_DIFF_SHARED)   // one x_true: its norm from the same kernel a slot of XT would take
+        lin(n, 1, 1, xtall, ones, nullptr, none, nullptr, none, nullptr, MVS_SQ, nullptr, ds(2, 0));
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const int nv = (int)groups[g].size();
+        vk(m, nv, 2, [&] { mv_pack(c, m, nv, ptrs(groups[g], bj, nullptr), Bi.at(g)); });
+        if (xt_cols) vk(n, nv, 2, [&] { mv_pack(c, n, nv, ptrs(groups[g], xtj, nullptr), XT.at(g)); });
+        lin(m, nv, 1, Bi.at(g), ones, nullptr, none, nullptr, none, U.at(g), MVS_SQ, nullptr, ds(0, g));   // u = b, ||b||^2
+        if (xt_cols) lin(n, nv, 1, XT.at(g), ones, nullptr, none, nullptr, none, nullptr, MVS_SQ, nullptr, ds(1, g));
+        zero_group(X.at(g), n, nv);                                            // x = 0
+        if (plsmr) zero_group(HB.at(g), n, nv);                                // lsmr_solver.m:26
+        if (hlsqr) zero_group(UN.at(g), n, nv);                                // u_aug = [b; 0] / beta
+    }
+    readback(3);
+    for (size_t g = 0; g < groups.size(); ++g)
+        for (size_t r = 0; r < groups[g].size(); ++r) {
+            const int j = groups[g][r];
+            nb[j] = std::sqrt(hs(0, g, r));
+            if (xt_in) nxt[j] = std::sqrt(xt_cols ? hs(1, g, r) : hs(2, 0, 0));
+            beta[j] = beta1[j] = nb[j];                                        // lsqr :7, lsmr :11, hybrid lsmr :7
+        }
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const int nv = (int)groups[g].size();
+        const auto& G = groups[g];
+        // lsqr :8 / hybrid lsmr :8 u = b / beta ; lsmr :12 only where beta > 0
+        vk(m, nv, 2, [&] { mv_div(c, m, nv, U.at(g), U.at(g), coef(G, 1.0, [&](int j) { return beta[j]; }), plsmr); });
+        product(At, nv, U.at(g), V.at(g));                                     // v_hat = A'*u
+        if (hlsqr)   // A_aug'*u_aug = A'*u + sqrt(lambda)*u_n
+            lin(n, nv, 2, V.at(g), ones, UN.at(g), coef(G, 0.0, [&](int j) { return sq[j]; }), nullptr, none, V.at(g),
+                MVS_SQ, nullptr, ds(0, g));
+        else
+            lin(n, nv, 1, V.at(g), ones, nullptr, none, nullptr, none, nullptr, MVS_SQ, nullptr, ds(0, g));
+    }
+    readback(1);
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const int nv = (int)groups[g].size();
+        const auto& G = groups[g];
+        for (size_t r = 0; r < G.size(); ++r) {
+            const int j = G[r];
+            alpha[j] = std::sqrt(hs(0, g, r));                                 // lsqr :11, lsmr :15, hybrid lsmr :14
+            rho_bar[j] = alpha[j];                                             // lsqr :15-16
+            phi_bar[j] = beta[j];
+            // lsmr_rotate's state: [alpha, alphabar, rho, rhobar, cbar, sbar, zetabar = alpha*beta (:19-23), 0, -]
+            const double r0[9] = {alpha[j], alpha[j], 1, 1, 1, 0, alpha[j] * beta[j], 0.0, 0.0};
+            std::copy(r0, r0 + 9, &rot[(size_t)9 * j]);
+        }
+        vk(n, nv, 2, [&] { mv_div(c, n, nv, V.at(g), V.at(g), coef(G, 1.0, [&](int j) { return alpha[j]; }), plsmr); });
+        if (!lsmr) copy_group(W.at(g), V.at(g), n, nv);                        // lsqr :14 w = v
+        if (plsmr) copy_group(H.at(g), V.at(g), n, nv);                        // lsmr :25 h = v
+        if (hlsmr)                                                             // hybrid lsmr :15-16 V(:,1)
+            vk(n, nv, 2, [&] { mv_unpack(c, n, nv, V.at(g), ptrs(G, [&](int j) { return Vj(j); }, dump)); });
+    }
+
+    // the running columns compacted into groups of 8 when that narrows a group or drops one
+    auto regather = [&]() {
+        std::vector<std::pair<size_t, size_t>> live;
+        size_t old_w = 0;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            old_w += (size_t)spmm_width((int)groups[g].size());
+            for (size_t r = 0; r < groups[g].size(); ++r)
+                if (groups[g][r] >= 0) live.push_back({g, r});
+        }
+        const size_t ng = (live.size() + SPMM_MAXV - 1) / SPMM_MAXV;
+        size_t new_w = 0;
+        for (size_t g = 0; g < ng; ++g) new_w += (size_t)spmm_width((int)std::min<size_t>(SPMM_MAXV, live.size() - g * SPMM_MAXV));
+        if (new_w >= old_w) return;
+        std::vector<GkVec*> sm = {&U, &Bi}, sn = {&V};
+        if (!hlsmr) sn.push_back(&X);                        // (hybrid LSMR re-forms x = V_k y every iteration)
+        for (GkVec* s : {&W, &H, &HB, &UN, &XT})
+            if (s->p) sn.push_back(s);
+        auto move = [&](GkVec* S, GkVec& tmp) {
+            for (size_t g = 0; g < ng; ++g) {
+                const int nv = (int)std::min<size_t>(SPMM_MAXV, live.size() - g * SPMM_MAXV);
+                MvSlots src;
+                for (int r = 0; r < SPMM_MAXV; ++r) {
+                    src.p[r] = nullptr;
+                    src.stride[r] = 1;
+                    if (r < nv) {
+                        const auto& from = live[g * SPMM_MAXV + r];
+                        src.stride[r] = spmm_width((int)groups[from.first].size());
+                        src.p[r] = S->at(from.first) + from.second;
+                    }
+                }
+                vk(S->len, nv, 2, [&] { mv_regather(c, S->len, nv, src, tmp.at(g)); });
+            }
+            std::swap(S->p, tmp.p);
+        };
+        for (GkVec* s : sm) move(s, tmp_m);
+        for (GkVec* s : sn) move(s, tmp_n);
+        std::vector<std::vector<int>> next(ng);
+        for (size_t i = 0; i < live.size(); ++i) next[i / SPMM_MAXV].push_back(groups[live[i].first][live[i].second]);
+        groups.swap(next);
+    };
+
+    int running = nrhs;
+    for (int k = 0; k < maxit && running > 0; ++k) {
+        const bool lastit = k == maxit - 1;
+        const bool bstep = !hlsmr || !lastit;                // hybrid lsmr :29: no new v after the last step
+        auto for_cols = [&](auto f) {
+            for (size_t g = 0; g < groups.size(); ++g)
+                for (size_t r = 0; r < groups[g].size(); ++r)
+                    if (groups[g][r] >= 0) f(groups[g][r], g, r);
+        };
+        // ---- u_hat = A*v - alpha*u, beta = norm(u_hat)  (lsqr :22-23, lsmr :34-35, hybrid lsmr :24-25) ----
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const int nv = (int)groups[g].size();
+            const auto& G = groups[g];
+            const MvCoef malpha = coef(G, 0.0, [&](int j) { return -alpha[j]; });
+            product(A, nv, V.at(g), Tm);
+            lin(m, nv, 2, Tm, ones, U.at(g), malpha, nullptr, none, U.at(g), MVS_SQ, nullptr, ds(0, g));
+            if (hlsqr)   // lower block of u_hat: (sqrt(lambda)*v) - (alpha*u_n)
+                lin(n, nv, 2, V.at(g), coef(G, 0.0, [&](int j) { return sq[j]; }), UN.at(g), malpha, nullptr, none,
+                    UN.at(g), MVS_SQ, nullptr, ds(1, g));
+        }
+        readback(hlsqr ? 2 : 1);
+        for_cols([&](int j, size_t g, size_t r) {
+            beta[j] = std::sqrt(hlsqr ? hs(0, g, r) + hs(1, g, r) : hs(0, g, r));
+            if (hlsmr) {
+                Bk[bks * j + (size_t)k * (maxit + 1) + k] = alpha[j];          // :23
+                Bk[bks * j + (size_t)k * (maxit + 1) + k + 1] = beta[j];       // :27
+            }
+        });
+        // ---- u = u_hat / beta ; v_hat = A'*u - beta*v, alpha = norm(v_hat)  (lsqr :24-27, lsmr :36-39) ----
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const int nv = (int)groups[g].size();
+            const auto& G = groups[g];
+            const MvCoef cbeta = coef(G, 1.0, [&](int j) { return beta[j]; });
+            vk(m, nv, 2, [&] { mv_div(c, m, nv, U.at(g), U.at(g), cbeta, plsmr); });
+            if (hlsqr) vk(n, nv, 2, [&] { mv_div(c, n, nv, UN.at(g), UN.at(g), cbeta, false); });
+            if (!bstep) continue;
+            const MvCoef mbeta = coef(G, 0.0, [&](int j) { return -beta[j]; });
+            product(At, nv, U.at(g), Tn);
+            if (hlsqr)   // (A'*u + sqrt(lambda)*u_n) - beta*v
+                lin(n, nv, 3, Tn, ones, UN.at(g), coef(G, 0.0, [&](int j) { return sq[j]; }), V.at(g), mbeta, V.at(g),
+                    MVS_SQ, nullptr, ds(0, g));
+            else
+                lin(n, nv, 2, Tn, ones, V.at(g), mbeta, nullptr, none, V.at(g), MVS_SQ, nullptr, ds(0, g));
+        }
+        if (bstep) {
+            readback(1);
+            for_cols([&](int j, size_t g, size_t r) { alpha[j] = std::sqrt(hs(0, g, r)); });
+        }
+        std::fill(stop.begin(), stop.end(), 0);
+        auto hist = [&](double* h, int j) -> double& { return h[(size_t)j * maxit + k]; };
+        // b - A*x of one group: ||.||^2 into sums; keep: the residual itself stays in Tm
+        auto residual = [&](size_t g, int nv, bool keep, double* sums) {
+            product(A, nv, X.at(g), Tm);
+            lin(m, nv, 2, Bi.at(g), ones, Tm, minus1, nullptr, none, keep ? Tm : nullptr, MVS_SQ, nullptr, sums);
+        };
+        if (!lsmr) {
+            // ---- LSQR: rotation :31-38, v = v_hat / alpha :28, x and w :40-41, error :43 ----
+            for_cols([&](int j, size_t, size_t) {
+                lsqr_rotate(beta[j], alpha[j], rho_bar[j], phi_bar[j], c_x[j], c_w[j]);
+                if (!hyb) {
+                    const double res = std::fabs(phi_bar[j]) / nb[j];          // :44
+                    if (res_hist) hist(res_hist, j) = res;
+                    stop[j] = res <= tol || lastit;                            // :46 (<=)
+                }
+            });
+            bool any_sum = errmode != MVS_NONE || hyb;
+            for (size_t g = 0; g < groups.size(); ++g) {
+                const int nv = (int)groups[g].size();
+                const auto& G = groups[g];
+                vk(n, nv, 6 + (errmode == MVS_DIFF ? 1 : 0), [&] {
+                    mv_lsqr_step(c, n, nv, V.at(g), X.at(g), W.at(g), coef(G, 1.0, [&](int j) { return alpha[j]; }),
+                                 coef(G, 0.0, [&](int j) { return c_x[j]; }), coef(G, 0.0, [&](int j) { return c_w[j]; }),
+                                 errmode, errD(g), ds(0, g));
+                });
+                // hybrid :43 b - A*x every iteration; lsqr :52 the explicit residual of the columns that stop now
+                bool need = hyb;
+                for (int j : G) need = need || (j >= 0 && stop[j]);
+                if (need) {
+                    residual(g, nv, false, ds(1, g));
+                    any_sum = true;
+                }
+            }
+            if (any_sum) readback(2);
+            for_cols([&](int j, size_t g, size_t r) {
+                if (err_hist && xt_in) hist(err_hist, j) = std::sqrt(hs(0, g, r)) / nxt[j];
+                if (hyb) {
+                    const double res = std::sqrt(hs(1, g, r)) / nb[j];
+                    if (res_hist) hist(res_hist, j) = res;
+                    stop[j] = res < tol || lastit;                             // hybrid :45 (<)
+                } else if (stop[j] && res_hist) {
+                    hist(res_hist, j) = std::sqrt(hs(1, g, r)) / nb[j];        // :52
+                }
+            });
+        } else if (plsmr) {
+            // ---- LSMR: rotations :42-67, v = v_hat / alpha :40, hbar / x / h :61-67, monitors :69-73 ----
+            for_cols([&](int j, size_t, size_t) {
+                double cfm[5], cfn[5];
+                lsmr_rotate(beta[j], alpha[j], &rot[(size_t)9 * j], &cf[(size_t)3 * j], cfm, cfn);
+            });
+            for (size_t g = 0; g < groups.size(); ++g) {
+                const int nv = (int)groups[g].size();
+                const auto& G = groups[g];
+                vk(n, nv, 8 + (errmode == MVS_DIFF ? 1 : 0), [&] {
+                    mv_lsmr_step(c, n, nv, V.at(g), X.at(g), H.at(g), HB.at(g),
+                                 coef(G, 1.0, [&](int j) { return alpha[j]; }),
+                                 coef(G, 0.0, [&](int j) { return cf[(size_t)3 * j]; }),
+                                 coef(G, 0.0, [&](int j) { return cf[(size_t)3 * j + 1]; }),
+                                 coef(G, 0.0, [&](int j) { return cf[(size_t)3 * j + 2]; }), k == 0, errmode, errD(g),
+                                 ds(0, g));
+                });
+                residual(g, nv, true, ds(1, g));                               // :69 r = b - A*x
+                product(At, nv, Tm, Tn);                                       // :71 A.'*r
+                lin(n, nv, 1, Tn, ones, nullptr, none, nullptr, none, nullptr, MVS_SQ, nullptr, ds(2, g));
+            }
+            readback(3);
+            for_cols([&](int j, size_t g, size_t r) {
+                const double nr = std::sqrt(hs(1, g, r));
+                const double res = nr / (nb[j] + EPSD);                        // :70
+                if (res_hist) hist(res_hist, j) = res;
+                if (ar_hist) hist(ar_hist, j) = std::sqrt(hs(2, g, r)) / (normA * std::max(nr, EPSD));   // :71
+                if (err_hist && xt_in) hist(err_hist, j) = std::sqrt(hs(0, g, r)) / nxt[j];              // :72-73
+                stop[j] = res < tol || lastit;                                 // :76 (<)
+            });
+        } else {
+            // ---- hybrid LSMR: V(:,k+1) :32-33, the projected solve :37-44, x = V_k y :45, monitors :47-48 ----
+            const int kk = k + 1;
+            for (size_t g = 0; g < groups.size() && bstep; ++g) {
+                const int nv = (int)groups[g].size();
+                const auto& G = groups[g];
+                vk(n, nv, 2, [&] { mv_div(c, n, nv, V.at(g), V.at(g), coef(G, 1.0, [&](int j) { return alpha[j]; }), false); });
+                vk(n, nv, 2, [&] {
+                    mv_unpack(c, n, nv, V.at(g), ptrs(G, [&](int j) { return Vj(j) + (size_t)kk * ldn; }, dump));
+                });
+            }
+            // (without a new v, :34 keeps the previous alpha: alpha[j] is untouched when !bstep)
+            for_cols([&](int j, size_t, size_t) {
+                dense::proj_hybrid_lsmr(&Bk[bks * j], maxit + 1, kk, alpha[j], beta[j], beta1[j], lambdas[j],
+                                        &Yh[(size_t)maxit * j]);
+            });
+            h2d(c, Yd, Yh.data(), sizeof(double) * Yh.size());
+            for_cols([&](int j, size_t, size_t) {
+                gemv<double>(c, n, kk, Vj(j), ldn, Yd + (size_t)maxit * j, xj(j), 0);                     // :45
+            });
+            for (size_t g = 0; g < groups.size(); ++g) {
+                const int nv = (int)groups[g].size();
+                const auto& G = groups[g];
+                vk(n, nv, 2, [&] { mv_pack(c, n, nv, ptrs(G, xj, dump), X.at(g)); });
+                if (errmode != MVS_NONE)                                       // :47
+                    lin(n, nv, 1, X.at(g), ones, nullptr, none, nullptr, none, nullptr, errmode, errD(g), ds(0, g));
+                residual(g, nv, false, ds(1, g));                              // :48
+            }
+            readback(2);
+            for_cols([&](int j, size_t g, size_t r) {
+                const double res = std::sqrt(hs(1, g, r)) / nb[j];
+                if (res_hist) hist(res_hist, j) = res;
+                if (err_hist && xt_in) hist(err_hist, j) = std::sqrt(hs(0, g, r)) / nxt[j];
+                stop[j] = res <= tol || lastit;                                // :50 (<=)
+            });
+        }
+        // ---- the columns that stop leave the batch with their x ----
+        bool left = false;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            auto& G = groups[g];
+            bool here = false;
+            for (int j : G) here = here || (j >= 0 && stop[j]);
+            if (!here) continue;
+            left = true;
+            const int nv = (int)G.size();
+            if (!hlsmr) vk(n, nv, 2, [&] { mv_unpack(c, n, nv, X.at(g), ptrs(G, xj, dump)); });
+            for (int& j : G)
+                if (j >= 0 && stop[j]) {
+                    niters[j] = k + 1;
+                    --running;
+                    j = -1;
+                }
+        }
+        if (left && running > 0) regather();
+    }
+    if (X_out)
+        for (int j = 0; j < nrhs; ++j) stage_out_n<double>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
+    return HGM_OK;
 }
 
 // explicit instantiations used by capi.cpp

@@ -9,6 +9,7 @@ from .core import spmv_ab, fused_plan_info  # noqa: F401
 from .core import SweepResult, gmres_lambda_sweep, proj_norms  # noqa: F401
 from .core import BatchResult, gmres_bounds_batch, spmm  # noqa: F401
 from .core import spmm_pert, gmres_bounds_mismatch, arnoldi_mismatch  # noqa: F401
+from .core import GKBatchResult, gk_batch, mv_axpby_norms  # noqa: F401
 from .core import (  # noqa: F401
     ABgmres_hybrid_bounds,
     ABgmres_nonhybrid_bounds,
@@ -47,4 +48,5 @@ __all__ = [
     "as_operator", "default_context", "HgmError", "OutputNotAssigned", "problems", "regtools", "analysis",
     "eig", "filter_factors", "ritz", "gmres_lambda_sweep", "proj_norms", "SweepResult",
     "gmres_bounds_batch", "spmm", "BatchResult", "spmm_pert", "gmres_bounds_mismatch", "arnoldi_mismatch",
+    "gk_batch", "mv_axpby_norms", "GKBatchResult",
 ]

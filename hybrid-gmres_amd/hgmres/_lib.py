@@ -37,6 +37,7 @@ def option_id(name):
 
 HGM_MGS, HGM_CGS2 = 0, 1
 HGM_SIDE_AB, HGM_SIDE_BA = 0, 1
+HGM_GK_LSQR, HGM_GK_LSMR = 0, 1
 HGM_DEVICE_PTRS = 1
 HGM_EXPLICIT_RESIDUAL = 2
 HGM_UNIQUE_ID_BYTES = 128
@@ -96,6 +97,7 @@ _SIGS = {
     "hgm_spmv_ab": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgm_spmm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64]),
     "hgm_spmm_pert": (c_int, [c_void_p, c_void_p, c_void_p, c_int, dp, c_void_p, c_int64, c_void_p, c_int64]),
+    "hgm_mv_axpby_norms": (c_int, [c_void_p, c_int64, c_int, dp, c_void_p, c_int64, dp, c_void_p, c_int64, c_void_p, c_int64, dp]),
     "hgm_proj_norms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp, dp]),
     "hgm_proj_norms_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp]),
     "hgm_fused_plan_info": (c_int, [c_void_p, c_void_p, c_void_p, dp, P(C.c_uint64), ip64, P(c_int)]),
@@ -122,6 +124,8 @@ _SIGS = {
                                           c_int, dp, c_int, c_int, dp, c_int64, dp, dp, P(c_int), P(c_int)]),
     "hgm_arnoldi_mismatch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, dp, c_int, dp, c_int, c_int, c_double, c_int,
                                      dp, dp, P(c_int)]),
+    "hgm_gk_batch": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, c_int64, c_int, dp, c_int64, c_double, c_int, dp,
+                             c_int, c_int, dp, c_int64, dp, dp, dp, P(c_int)]),
     "hgm_lsqr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, P(c_int)]),
     "hgm_lsmr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, dp, P(c_int)]),
     "hgm_arnoldi": (c_int, [c_void_p, c_void_p, c_void_p, dp, c_int, c_int, c_double, c_int, dp, dp, P(c_int)]),

@@ -190,6 +190,69 @@ def error_vs_noise_level(A, B, b_exact, x_true, noise_levels, *, maxit, tol=1e-6
     return out
 
 
+def equivalence_vs_noise_level(A, b_exact, x_true, noise_levels, *, maxit, tol=1e-6, lam=1e-3, seed=0, ctx=None) -> dict:
+    """``run_equivalence_plots.m:12-22`` (the same ``b`` through all eight solvers, ``B = A'``: AB-GMRES == LSQR and
+    BA-GMRES == LSMR) over the noise levels of ``plot_error_vs_noise_level.m:28-32``, each solver's loop over the
+    levels as ONE lockstep solve: four :func:`hgmres.core.gmres_bounds_batch` calls (the four ``*_bounds`` solvers,
+    the hybrid ones at ``lam``) and four :func:`hgmres.core.gk_batch` calls (``lsqr``, ``lsmr``, ``hybrid_lsqr``,
+    ``hybrid_lsmr``).  ``B`` is the device transpose of ``A``.  The right-hand sides are drawn exactly as
+    :func:`error_vs_noise_level` draws them.  Calls take at most 64 levels each.
+
+    Returns ``noise_levels``, the noisy ``Bm`` (``m x nlevels``), ``final_errors_<key>`` / ``niters_<key>`` for the
+    keys 'ab', 'ba', 'hab', 'hba' (non-hybrid / hybrid GMRES) and 'lsqr', 'lsmr', 'hybrid_lsqr', 'hybrid_lsmr', and
+    ``gap_ab_lsqr`` / ``gap_ba_lsmr``: the largest relative gap ``|e1 - e2| / |e2|`` between the two error
+    histories of a pair, over every level and the iterations both solvers ran."""
+    levels = np.asarray(noise_levels, dtype=np.float64).reshape(-1)
+    nl = levels.size
+    if nl < 1:
+        raise ValueError("noise_levels is empty")
+    m, n = A.shape
+    b_exact = np.asarray(b_exact, dtype=np.float64).reshape(-1)
+    x_true = np.asarray(x_true, dtype=np.float64).reshape(-1)
+    if b_exact.size != m or x_true.size != n:
+        raise ValueError(f"b_exact / x_true have lengths {b_exact.size} / {x_true.size}, expected {m} / {n}")
+    if not (np.isfinite(lam) and lam >= 0):
+        raise ValueError("lam must be finite and >= 0")
+    maxit = int(maxit)
+    if maxit < 1:
+        raise ValueError("maxit must be >= 1")
+    rng = np.random.default_rng(seed)
+    nbe = np.linalg.norm(b_exact)
+    Bm = np.empty((m, nl), order="F")
+    for i, level in enumerate(levels):                         # plot_error_vs_noise_level.m:29-32
+        noise = rng.standard_normal(m)
+        Bm[:, i] = b_exact + noise / np.linalg.norm(noise) * level * nbe
+    ctx = ctx or (A.ctx if isinstance(A, core.SparseOperator) else core.default_context())
+    Ao = core.as_operator(A, ctx)                              # uploaded once, reused by every solve
+    Bo = Ao.T                                                  # :5 B = A'
+    out = {"noise_levels": levels, "Bm": Bm, "lambda": float(lam)}
+    hist = {}
+    for key in ("ba", "lsmr", "ab", "lsqr", "hba", "hybrid_lsmr", "hab", "hybrid_lsqr"):       # :12-22
+        fin, nit = np.full(nl, np.nan), np.zeros(nl, dtype=int)
+        eh = np.full((maxit, nl), np.nan)
+        for lo in range(0, nl, 64):                            # at most 64 columns per call
+            hi = min(nl, lo + 64)
+            lams = np.full(hi - lo, float(lam))
+            if key in core.GK_KINDS:
+                R = core.gk_batch(Ao, Bm[:, lo:hi], x_true, tol, maxit, key, At=Bo, ctx=ctx,
+                                  lambdas=lams if core.GK_KINDS[key][1] else None)
+            else:
+                R = core.gmres_bounds_batch(Ao, Bo, Bm[:, lo:hi], x_true, tol, maxit, key[-2:],
+                                            lambdas=lams if key[0] == "h" else None, ctx=ctx)
+            ok = R.niters >= 1
+            fin[lo:hi][ok] = R.error_norm[R.niters[ok] - 1, np.nonzero(ok)[0]]     # err(end)
+            nit[lo:hi] = R.niters
+            eh[:, lo:hi] = R.error_norm
+        out[f"final_errors_{key}"] = fin
+        out[f"niters_{key}"] = nit
+        hist[key] = eh
+    for pair, k1, k2 in (("ab_lsqr", "ab", "lsqr"), ("ba_lsmr", "ba", "lsmr")):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            g = np.abs(hist[k1] - hist[k2]) / np.abs(hist[k2])
+        out["gap_" + pair] = float(np.nanmax(g)) if np.any(np.isfinite(g)) else float("nan")
+    return out
+
+
 def _fro(E):
     """``norm(E, 'fro')`` of a scipy matrix, an array or a device operator."""
     if isinstance(E, core.SparseOperator):

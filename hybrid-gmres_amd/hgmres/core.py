@@ -1035,6 +1035,130 @@ def hybrid_lsmr_solver(A, b, x_true, tol, maxit, lambda_, *, ctx=None, At=None):
     return x, err[:k].copy(), res[:k].copy(), k
 
 
+class GKBatchResult:
+    """Outputs of :func:`gk_batch`.  ``x``: ``n x nrhs``; ``error_norm``, ``residual_norm``, ``ar_norm``:
+    ``maxit x nrhs`` (row k-1 = iteration k; NaN past ``niters[j]``; ``ar_norm`` is all NaN except for
+    ``kind='lsmr'``); ``niters``: per column."""
+
+    def __init__(self, x, error_norm, residual_norm, ar_norm, niters):
+        self.x, self.error_norm, self.residual_norm, self.ar_norm = x, error_norm, residual_norm, ar_norm
+        self.niters = niters
+
+
+GK_KINDS = {"lsqr": (L.HGM_GK_LSQR, 0), "lsmr": (L.HGM_GK_LSMR, 0), "hybrid_lsqr": (L.HGM_GK_LSQR, 1),
+            "hybrid_lsmr": (L.HGM_GK_LSMR, 1)}
+
+
+def gk_batch(A, Bm, x_true, tol, maxit, kind, *, lambdas=None, At=None, ctx=None):
+    """``nrhs`` lockstep solves of one Golub-Kahan solver against one operator (``hgm_gk_batch``): column j of
+    every output is what ``lsqr_solver`` / ``lsmr_solver`` / ``hybrid_lsqr_solver`` / ``hybrid_lsmr_solver``
+    (``kind`` 'lsqr', 'lsmr', 'hybrid_lsqr', 'hybrid_lsmr') returns for ``b = Bm[:, j]``, ``x_true[:, j]`` and
+    ``lambdas[j]`` (the hybrid kinds need ``lambdas``).  A 1-D ``Bm`` with several lambdas is one ``b`` shared by
+    every column: a hybrid solver's lambda sweep.  ``x_true`` is ``n x nrhs``, one vector shared by every column,
+    or None (the error histories stay NaN).  ``At`` defaults to the device transpose of ``A``.  The operators'
+    entries are read once per group of up to 8 running columns and pass; a finished column leaves the batch."""
+    if str(kind).lower() not in GK_KINDS:
+        raise ValueError(f"kind must be one of {sorted(GK_KINDS)}, not {kind!r}")
+    kd, hybrid = GK_KINDS[str(kind).lower()]
+    m, n = A.shape
+    maxit = int(maxit)
+    lam = None
+    if lambdas is not None:
+        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+    if hybrid and lam is None:
+        raise ValueError(f"kind {kind!r} needs lambdas (one per column)")
+    Bm = np.asarray(Bm, dtype=np.float64)
+    shared_b = Bm.ndim == 1 and lam is not None and lam.size > 1
+    if shared_b:
+        if Bm.shape[0] != m:
+            raise ValueError(f"b has length {Bm.shape[0]}, expected {m}")
+        nrhs = lam.size
+    else:
+        if Bm.ndim == 1:
+            Bm = Bm.reshape(-1, 1)
+        if Bm.ndim != 2 or Bm.shape[0] != m or Bm.shape[1] < 1:
+            raise ValueError(f"Bm has shape {Bm.shape}, expected ({m}, nrhs)")
+        nrhs = Bm.shape[1]
+    if nrhs > 64:
+        raise ValueError(f"at most 64 columns per call, not {nrhs}")
+    if lam is not None and lam.size != nrhs:
+        raise ValueError(f"lambdas has {lam.size} entries, expected one per column ({nrhs})")
+    if hybrid and not (np.all(np.isfinite(lam)) and np.all(lam >= 0)):
+        raise ValueError("every lambda must be finite and >= 0")
+    xt, ldxt = None, 0
+    if x_true is not None:
+        xt = np.asarray(x_true, dtype=np.float64)
+        if xt.ndim == 1 or (xt.ndim == 2 and xt.shape[1] == 1 and nrhs != 1):
+            xt = _f64(xt, n, "x_true")                              # one column shared by every right-hand side
+        elif xt.shape != (n, nrhs):
+            raise ValueError(f"x_true has shape {xt.shape}, expected ({n},) or ({n}, {nrhs})")
+        else:
+            xt, ldxt = np.asfortranarray(xt), max(n, 1)
+    if maxit < 1:
+        raise ValueError("maxit must be >= 1")
+    if At is not None and tuple(At.shape) != (n, m):
+        raise ValueError(f"At has shape {tuple(At.shape)}, expected ({n}, {m})")
+    ctx, Ao, Ato = _gkb_ops(A, ctx, At)
+    Bf = np.ascontiguousarray(Bm) if shared_b else np.asfortranarray(Bm)
+    X = np.full((n, nrhs), np.nan, order="F")
+    err, res, ar = (np.full((maxit, nrhs), np.nan, order="F") for _ in range(3))
+    nit = np.zeros(nrhs, dtype=np.int32)
+    o = _opts()
+    _check(L.load().hgm_gk_batch(ctx.handle, C.byref(o), Ao._h, Ato._h, _dp(Bf), 0 if shared_b else max(m, 1), nrhs,
+                                 _dp(xt), ldxt, float(tol), maxit, _dp(lam), kd, hybrid, _dp(X), max(n, 1), _dp(err),
+                                 _dp(res), _dp(ar), nit.ctypes.data_as(C.POINTER(C.c_int))), ctx)
+    return GKBatchResult(X, err, res, ar, nit.astype(int))
+
+
+def mv_axpby_norms(a, X, b, Y, ctx=None):
+    """``Out[:, r] = (a[r] * X[:, r]) + (b[r] * Y[:, r])`` for ``n x nvec`` host arrays (``1 <= nvec <= 8``) and
+    ``sumsq[r] = sum_i Out[i, r]**2`` through ``hgm_mv_axpby_norms``, the interleaved vector kernel of
+    :func:`gk_batch` (gkmv.hip): products and sum rounded separately, a fixed summation order, and a column's bits
+    independent of ``nvec``, its position and the other columns.  Returns ``(Out, sumsq)``."""
+    X = np.asarray(X, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    if Y.ndim == 1:
+        Y = Y.reshape(-1, 1)
+    if X.ndim != 2 or Y.shape != X.shape:
+        raise ValueError(f"X and Y have shapes {X.shape} and {Y.shape}, expected the same (n, nvec)")
+    n, nv = X.shape
+    if not 1 <= nv <= 8:
+        raise ValueError(f"mv_axpby_norms takes 1 to 8 vectors, not {nv}")
+    af = _coefs_any(a, nv, "a")
+    bf = _coefs_any(b, nv, "b")
+    ctx = ctx or default_context()
+    lib = L.load()
+    Xf, Yf = np.asfortranarray(X), np.asfortranarray(Y)
+    Out = np.empty((n, nv), order="F")
+    ss = np.zeros(nv)
+    ptr = [C.c_void_p() for _ in range(3)]
+    ld = max(n, 1)
+    try:
+        for p_ in ptr:
+            _check(lib.hgm_dev_alloc(ctx.handle, 8 * ld * nv, C.byref(p_)), ctx)
+        if n:
+            _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
+            _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[1], Yf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
+        _check(lib.hgm_mv_axpby_norms(ctx.handle, n, nv, _dp(af), ptr[0], ld, _dp(bf), ptr[1], ld, ptr[2], ld, _dp(ss)),
+               ctx)
+        if n:
+            _check(lib.hgm_memcpy_d2h(ctx.handle, Out.ctypes.data_as(C.c_void_p), ptr[2], 8 * n * nv), ctx)
+    finally:
+        for p_ in ptr:
+            if p_.value:
+                lib.hgm_dev_free(ctx.handle, p_)
+    return Out, ss
+
+
+def _coefs_any(v, nv, name):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+    if a.size != nv:
+        raise ValueError(f"{name} has {a.size} entries, expected one per vector ({nv})")
+    return a
+
+
 def arnoldi(A, B, b, k, gcv_type="ba", *, ctx=None, breakdown_tol=1e-12, orth="mgs"):
     """Arnoldi part of ``gcv_function.m:3-33``: returns (H, beta, kdone)."""
     ctx, Ao, Bo = _ops(A, B, ctx)

@@ -23,6 +23,9 @@
  *                               over *_hybrid_bounds.m (one Arnoldi for every lambda)
  *   hgm_gmres_bounds_batch   <- the loop over the noise levels of plot_error_vs_noise_level.m:28-54 over the
  *                               four *_bounds.m (many right-hand sides, one operator pair)
+ *   hgm_gk_batch             <- the same loop over lsqr_solver.m, hybrid_lsqr_solver.m, lsmr_solver.m and
+ *                               hybrid_lsmr_solver.m (run_equivalence_plots.m:12-22 puts the two solver families
+ *                               side by side), and a hybrid Golub-Kahan solver's lambda loop (one shared b)
  *   hgm_gmres_bounds_mismatch <- the loop over the mismatch levels c of plot_error_vs_mismatch_norm.m:23-61 /
  *                               run_2D_phantom.m:79-102 (B_pert = A' + c*E: one b, many back-projectors that
  *                               differ in a scalar; no B_pert is formed)
@@ -356,6 +359,13 @@ HGM_API int hgm_spmm(hgm_ctx*, const hgm_mat* A, int nvec, const double* X_dev, 
  * differs from B0's. */
 HGM_API int hgm_spmm_pert(hgm_ctx*, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs_host,
                           const double* X_dev, int64_t ldx, double* Y_dev, int64_t ldy);
+/* Out(:,r) = (a[r]*X(:,r)) + (b[r]*Y(:,r)), r < nvec <= 8, column-major device pointers (ld >= n), coefficients
+ * on the host; sumsq_host (optional): nvec values, sum_i Out(i,r)^2 in a fixed order.  Products and sum rounded
+ * separately.  A column's bits do not depend on nvec, its position or the other columns.  (The interleaved
+ * vector kernel of hgm_gk_batch on its own.) */
+HGM_API int hgm_mv_axpby_norms(hgm_ctx*, int64_t n, int nvec, const double* a, const double* X_dev, int64_t ldx,
+                               const double* b, const double* Y_dev, int64_t ldy, double* Out_dev, int64_t ldo,
+                               double* sumsq_host);
 /* Multi-coefficient projected norms (the monitors of hgm_gmres_bounds_sweep), on device pointers:
  * V is rows x k column-major with leading dimension ldv >= rows, Y is k x nlam column-major (ldy >= k),
  * t has rows entries (NULL: zeros).  For every column l, in ONE pass over V (the rows x nlam product is
@@ -486,6 +496,28 @@ HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx*, const hgm_opts*, const hgm_mat* 
         const hgm_mat* E, const double* coefs, int ncoef, const double* b, const double* x_true, double tol,
         int maxit, const double* lambdas, int side, int hybrid, double* X, int64_t ldx,
         double* error_hist, double* residual_hist, int* niters, int* col_status);
+/* nrhs lockstep solves of one Golub-Kahan solver (kind, hybrid) against one operator pair (A, At): column j of
+ * every output is what the single solver returns for b = Bm(:,j), x_true = XT(:,j), lambda = lambdas[j]:
+ *     kind LSQR, hybrid 0: hgm_lsqr_solver_ex        kind LSQR, hybrid 1: hgm_hybrid_lsqr_solver
+ *     kind LSMR, hybrid 0: hgm_lsmr_solver_ex        kind LSMR, hybrid 1: hgm_hybrid_lsmr_solver
+ * (lsqr_solver.m:44-46 with the explicit final residual of :52 at the column's own stop; hybrid_lsqr_solver.m:5-45;
+ * lsmr_solver.m:69-76 with the explicit monitors, the HGM_EXPLICIT_RESIDUAL form; hybrid_lsmr_solver.m:21-51.)
+ * Per iteration the operators' entries are read once per group of up to 8 running columns (hgm_spmm's kernel) and
+ * the scalars of all running columns come back in at most three transfers.
+ * Bm: m x nrhs (host, ldb >= m), or ONE b shared by every column (ldb == 0: a hybrid solver's lambda sweep).
+ * x_true: n x nrhs (ldxt >= n), one shared column (ldxt == 0), or NULL (the error histories stay NaN).
+ * lambdas: nrhs entries, required with hybrid = 1, ignored (may be NULL) otherwise.  error_hist / residual_hist /
+ * ar_hist (each optional): maxit x nrhs column-major, NaN past niters[j]; ar_hist is written for (LSMR, 0) only.
+ * X: n x nrhs (ldx >= n), reference pixel order.  Every column has its own stopping iteration; a finished column
+ * leaves the batch.  A column whose scalars go non-finite (b = 0) behaves as in the single solver and does not
+ * disturb the others.  Refused: HGM_E_ARG for fp32 operators, parity mode, HGM_DEVICE_PTRS, nrhs < 1 or > 64,
+ * maxit < 1, a bad kind, At NULL or not size(A'), and with hybrid = 1 missing, negative or non-finite lambdas;
+ * HGM_E_UNSUPPORTED on a communicator or a context with a host all-reduce hook. */
+enum hgm_gk_kind { HGM_GK_LSQR = 0, HGM_GK_LSMR = 1 };
+HGM_API int hgm_gk_batch(hgm_ctx*, const hgm_opts*, const hgm_mat* A, const hgm_mat* At,
+        const double* Bm, int64_t ldb, int nrhs, const double* x_true, int64_t ldxt, double tol, int maxit,
+        const double* lambdas, int kind, int hybrid, double* X, int64_t ldx,
+        double* error_hist, double* residual_hist, double* ar_hist, int* niters);
 HGM_API int hgm_lsqr_solver_ex(hgm_ctx* ctx, const hgm_opts* opts, const hgm_mat* A,
                                const hgm_mat* At, const double* b, const double* x_true, double tol,
                                int maxit, double* x, double* error_norm, double* residual_norm,
@@ -554,7 +586,8 @@ HGM_API int hgm_eig(int n, const double* A, double* wr, double* wi, double* V);
  * 0 = SpMV on A (ray-major), 1 = SpMV on B/Aᵀ (pixel-major), 2 = MGS pass, 3 = the one-pass A*(B*q),
  * 4 = the launches of a hgm_proj_norms / hgm_proj_norms_loop call, 5 = the launches of an hgm_spmm
  * or hgm_spmm_pert product, pack/unpack included (and each operator pass group of hgm_gmres_bounds_batch,
- * hgm_gmres_bounds_mismatch and hgm_arnoldi_mismatch).
+ * hgm_gmres_bounds_mismatch, hgm_arnoldi_mismatch and hgm_gk_batch), 6 = the interleaved multi-vector kernels of
+ * hgm_gk_batch and hgm_mv_axpby_norms (recurrences, divisions, sums, packs / unpacks, re-gathers).
  * enable: 0 = off, 1 = every class, HGM_TIMING_CLASSES(mask) = only the classes whose
  * bit is set (each timed launch carries events, so time only what is read). */
 #define HGM_TIMING_CLASSES(mask) (0x100 | (mask))

@@ -34,6 +34,12 @@
  *        plot_error_vs_mismatch_norm.m:23-61 over one {AB,BA}gmres_{hybrid,nonhybrid}_bounds solver as ONE lockstep
  *        sweep (hgm_gmres_bounds_mismatch): column j is the solve of b with B = B0 + coefs(j)*E and lambdas(j); no
  *        B0 + c*E is formed.  x_true is n x 1 or []; outputs as 'gmres_bounds_batch'.  Always the production kernels.
+ *   hgmres_mex('gk_batch', kind, A,Bm,x_true,tol,maxit[,lambdas])
+ *        -> [X, error_hist, residual_hist, ar_hist, niters]   one Golub-Kahan solver (kind 'lsqr', 'lsmr', 'hybrid_lsqr',
+ *        'hybrid_lsmr') for every column of Bm as ONE lockstep batch (hgm_gk_batch): column j is the solve of Bm(:,j)
+ *        with lambdas(j); an m x 1 Bm with several lambdas is one b shared by every column (a lambda sweep).  x_true is
+ *        n x 1 (shared), n x nrhs or []; maxit x nrhs histories (NaN past niters(j)); ar_hist is filled for 'lsmr' only.
+ *        Always the production kernels.
  *   hgmres_mex('device', d)                      select the HIP device (default 0)
  *   hgmres_mex('parity', 'auto'|'on'|'off')      summation orders (below; default 'auto')
  *
@@ -596,6 +602,74 @@ static void bounds_mismatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     if (nlhs > 4) plhs[4] = cs;
 }
 
+/* [X, error_hist, residual_hist, ar_hist, niters] = hgmres_mex('gk_batch', kind, A, Bm, x_true, tol, maxit [, lambdas]).
+ * kind: 'lsqr', 'lsmr', 'hybrid_lsqr' or 'hybrid_lsmr'.  Bm is m x nrhs, or m x 1 with several lambdas (one b shared
+ * by every column).  The kind, every size and the lambdas are checked before a device is touched. */
+static void gk_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    char kd[16];
+    if (!mxIsChar(prhs[1]) || mxGetString(prhs[1], kd, sizeof kd) != 0)
+        fail("hgmres:arg", "hgmres: kind is 'lsqr', 'lsmr', 'hybrid_lsqr' or 'hybrid_lsmr'");
+    int kind = 0, hybrid = 0;
+    if (!strcmp(kd, "lsqr")) kind = HGM_GK_LSQR;
+    else if (!strcmp(kd, "lsmr")) kind = HGM_GK_LSMR;
+    else if (!strcmp(kd, "hybrid_lsqr")) { kind = HGM_GK_LSQR; hybrid = 1; }
+    else if (!strcmp(kd, "hybrid_lsmr")) { kind = HGM_GK_LSMR; hybrid = 1; }
+    else fail("hgmres:arg", "hgmres: kind is 'lsqr', 'lsmr', 'hybrid_lsqr' or 'hybrid_lsmr'");
+    need_double(prhs[2], "A");
+    const int64_t m = (int64_t)mxGetM(prhs[2]), n = (int64_t)mxGetN(prhs[2]);
+    need_double(prhs[3], "Bm");
+    int64_t nb = (int64_t)mxGetN(prhs[3]);
+    if (mxIsSparse(prhs[3]) || (int64_t)mxGetM(prhs[3]) != m || nb < 1 || nb > 64)
+        fail("hgmres:arg", "hgmres: Bm must be a dense size(A,1) x nrhs matrix with 1 <= nrhs <= 64");
+    const double* lam = NULL;
+    int64_t ldb = m > 0 ? m : 1;
+    if (hybrid) {
+        if (nrhs < 8) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per column)");
+        need_double(prhs[7], "lambdas");
+        const int64_t nl = (int64_t)mxGetNumberOfElements(prhs[7]);
+        if (mxIsSparse(prhs[7]) || nl < 1 || nl > 64 || (nl != nb && nb != 1))
+            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per column");
+        if (nb == 1 && nl > 1) {                          /* one b shared by every lambda */
+            nb = nl;
+            ldb = 0;
+        }
+        lam = mxGetDoubles(prhs[7]);
+        for (int64_t j = 0; j < nb; ++j)
+            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
+    }
+    const double* xt = NULL;
+    int64_t ldxt = 0;
+    if (!mxIsEmpty(prhs[4])) {
+        need_double(prhs[4], "x_true");
+        const int64_t xm = (int64_t)mxGetM(prhs[4]), xn = (int64_t)mxGetN(prhs[4]);
+        if (mxIsSparse(prhs[4]) || xm != n || (xn != 1 && xn != nb))
+            fail("hgmres:arg", "hgmres: x_true must be dense, size(A,2) x 1 or size(A,2) x nrhs, or []");
+        xt = mxGetDoubles(prhs[4]);
+        ldxt = xn == 1 && nb != 1 ? 0 : n;
+    }
+    const double tol = scalar(prhs[5], "tol");
+    const int maxit = maxit_of(prhs[6]);
+    hgm_mat* A = op(prhs[2], "A");
+    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
+    hgm_mat* At = transpose_op(A);
+    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nb, mxREAL);
+    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
+    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
+    mxArray* a = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
+    int* nit = (int*)mxCalloc((size_t)nb, sizeof(int));
+    for (int64_t i = 0; i < n * nb; ++i) mxGetDoubles(X)[i] = (double)NAN;
+    check(hgm_gk_batch(ctx(), NULL, A, At, mxGetDoubles(prhs[3]), ldb, (int)nb, xt, ldxt, tol, maxit, lam, kind,
+                       hybrid, mxGetDoubles(X), n > 0 ? n : 1, mxGetDoubles(e), mxGetDoubles(r), mxGetDoubles(a), nit));
+    mxArray* ni = mxCreateDoubleMatrix((mwSize)nb, 1, mxREAL);
+    for (int64_t j = 0; j < nb; ++j) mxGetDoubles(ni)[j] = (double)nit[j];
+    mxFree(nit);
+    plhs[0] = X;
+    if (nlhs > 1) plhs[1] = e;
+    if (nlhs > 2) plhs[2] = r;
+    if (nlhs > 3) plhs[3] = a;
+    if (nlhs > 4) plhs[4] = ni;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char fn[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], fn, sizeof fn) != 0)
@@ -630,6 +704,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(fn, "gmres_bounds_batch")) {
         nargs(nrhs, 8, 9, fn);
         bounds_batch(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(fn, "gk_batch")) {
+        nargs(nrhs, 6, 7, fn);
+        gk_batch(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(fn, "gmres_bounds_mismatch")) {
         nargs(nrhs, 10, 11, fn);
         bounds_mismatch(nlhs, plhs, nrhs, prhs);
