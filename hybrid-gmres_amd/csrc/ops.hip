@@ -870,6 +870,74 @@ __global__ __launch_bounds__(BS) void k_backproj(int N, int p, int na, const dou
     }
 }
 
+// --------------------------------------------------------------------------
+// Unmatched pixel-driven back-projector of the fan-beam geometry (mirrors
+// hgmres/problems.py::fan_pixel_backprojector; include/hgmres.h states the definition): for every
+// pixel centre and source, linear interpolation in the fan angle between the two rays that
+// bracket the pixel.  s(d) = across co[d] - along so[d] = |v| sin(gamma - omega_d) is the side of
+// ray d the centre lies on; d0 is the last d with s(d) >= 0, defined by a bisection over d.
+// The kernel guesses d0 from gamma = atan2(across, along) (inexact: the device atan2 and the
+// division are not the twin's) and keeps the guess only where the computed signs bracket,
+// s(g) >= 0 > s(g+1) (g = -1 / p-1: the one sign that exists); otherwise it runs the bisection
+// itself, so d0 is the bisection's wherever the signs are monotone in d.  co/so are interleaved
+// (one 16-B load per side) and left to the caches: the lanes of a wave are neighbouring pixels
+// whose brackets lie within a few 128-B lines of each other.  One thread per STORED pixel row.
+// --------------------------------------------------------------------------
+template <bool FILL, typename T>
+__global__ __launch_bounds__(BS) void k_fan_backproj(int N, int p, int na, double D, double dom, double doff,
+                                                     const double* __restrict__ cb, const double* __restrict__ sb,
+                                                     const double2* __restrict__ cs, int tile, int super,
+                                                     int64_t* __restrict__ counts, const int64_t* __restrict__ rp,
+                                                     int32_t* __restrict__ ci, T* __restrict__ val) {
+    const int64_t n = (int64_t)N * N;
+    const double half = N / 2.0;
+    const double gshift = (p - 1) / 2.0 - doff;
+    for (int64_t s = (int64_t)blockIdx.x * BS + threadIdx.x; s < n; s += (int64_t)gridDim.x * BS) {
+        int64_t r, c;
+        if (tile > 1 || super > 1) pixel_rc(N, tile, super, s, r, c);
+        else { r = s % N; c = s / N; }
+        const double xc = ((double)c - half) + 0.5;
+        const double yc = ((double)(N - 1 - r) - half) + 0.5;
+        int64_t cnt = 0;
+        const int64_t o = FILL ? rp[s] : 0;
+        for (int a = 0; a < na; ++a) {
+            const double ca = cb[a], sa = sb[a];
+            const double vx = xc - D * ca, vy = yc - D * sa;
+            const double along = -(vx * ca + vy * sa);
+            const double across = sa * vx - ca * vy;
+            auto side = [&](int d) {
+                const double2 w = cs[d];
+                return across * w.x - along * w.y;
+            };
+            int d0 = (int)fmin(fmax(floor(atan2(across, along) / dom + gshift), -1.0), (double)(p - 1));
+            double s0 = d0 >= 0 ? side(d0) : 0.0;
+            double s1 = d0 + 1 < p ? side(d0 + 1) : -1.0;
+            if (!(s0 >= 0 && s1 < 0)) {
+                int lo = -1, hi = p;
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (side(mid) >= 0) lo = mid;
+                    else hi = mid;
+                }
+                d0 = lo;
+                if (d0 >= 0 && d0 < p - 1) { s0 = side(d0); s1 = side(d0 + 1); }
+            }
+            if (d0 < 0 || d0 >= p - 1) continue;      // outside the fan [omega_0, omega_{p-1})
+            const double w1 = s0 / (s0 - s1), w0 = 1.0 - w1;
+            const int64_t col = (int64_t)a * p + d0;
+            if (w0 > 0) {
+                if (FILL) { ci[o + cnt] = (int32_t)col; val[o + cnt] = (T)w0; }
+                ++cnt;
+            }
+            if (w1 > 0) {
+                if (FILL) { ci[o + cnt] = (int32_t)(col + 1); val[o + cnt] = (T)w1; }
+                ++cnt;
+            }
+        }
+        if (!FILL) counts[s] = cnt;
+    }
+}
+
 hgm_mat* backprojector(hgm_ctx* c, int N, int n_angles, double det_offset, int dtype, int tile, int super) {
     HGM_REQUIRE(N > 0 && n_angles > 0, "backprojector: N and n_angles must be positive");
     if (tile < 1) tile = 1;
@@ -1056,6 +1124,85 @@ hgm_mat* fanbeam(hgm_ctx* c, int N, int n_angles, double R, double span, double 
         else
             k_fanbeam<true, double><<<g, BS, 0, st>>>(N, p, m, D, dcb, dsb, dco, dso, nullptr, M->rp, M->ci,
                                                       (double*)M->val, tile, super);
+        HGM_HIP(hipGetLastError());
+        HGM_HIP(hipStreamSynchronize(st));
+    } catch (...) {
+        release();
+        mat_free(M);
+        throw;
+    }
+    release();
+    return M;
+}
+
+hgm_mat* fan_backprojector(hgm_ctx* c, int N, int n_angles, double R, double span, double det_offset, int dtype,
+                           int tile, int super) {
+    HGM_REQUIRE(N > 0 && n_angles > 0, "fan_backprojector: N and n_angles must be positive");
+    HGM_REQUIRE(R > 1.0 / std::sqrt(2.0),
+                "fan_backprojector: the source must lie outside the image (R > 1/sqrt(2))");
+    if (tile < 1) tile = 1;
+    if (super < 2) super = 0;
+    HGM_REQUIRE(N % tile == 0 && (super == 0 || (N % super == 0 && super % tile == 0)),
+                "fan_backprojector: tile must divide N (and super), super must divide N");
+    if (!(span > 0)) span = 2.0 * std::asin(1.0 / (std::sqrt(2.0) * R));
+    HGM_REQUIRE(span < M_PI, "fan_backprojector: span must be below pi");
+    hipStream_t st = c->stream;
+    const int p = (int)std::ceil(std::sqrt(2.0) * N);
+    const int64_t n = (int64_t)N * N, m = (int64_t)p * n_angles;
+    HGM_REQUIRE(m <= INT32_MAX, "fan_backprojector: column index overflow");
+    const double D = R * N, dom = span / p;
+    // geometry on the host with C libm, the tables of fanbeam(); co/so interleaved per detector
+    std::vector<double> geo_h(2 * (size_t)n_angles + 2 * (size_t)p);
+    double *cb = geo_h.data(), *sb = cb + n_angles, *cs = sb + n_angles;
+    for (int a = 0; a < n_angles; ++a) {
+        const double b = a * (2.0 * M_PI / n_angles);
+        cb[a] = std::cos(b);
+        sb[a] = std::sin(b);
+    }
+    for (int d = 0; d < p; ++d) {
+        const double w = (((double)d - (p - 1) / 2.0) + det_offset) * dom;
+        cs[2 * d] = std::cos(w);
+        cs[2 * d + 1] = std::sin(w);
+    }
+    // the double2 loads of cs need 16-B alignment: pad the two angle tables to an even count
+    const size_t na2 = ((size_t)n_angles + 1) & ~(size_t)1;
+    double* geo = nullptr;
+    int64_t *counts = nullptr, *rp = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    hgm_mat* M = nullptr;
+    auto release = [&]() {
+        (void)hipFree(geo); (void)hipFree(counts); (void)hipFree(rp); (void)hipFree(tmp);
+    };
+    try {
+        HGM_HIP(hipMalloc(&geo, 8 * (2 * na2 + 2 * (size_t)p)));
+        double *dcb = geo, *dsb = geo + na2;
+        const double2* dcs = reinterpret_cast<const double2*>(geo + 2 * na2);
+        HGM_HIP(hipMalloc(&counts, 8 * (n + 1)));
+        HGM_HIP(hipMalloc(&rp, 8 * (n + 1)));
+        HGM_HIP(hipMemcpyAsync(dcb, cb, 8 * n_angles, hipMemcpyHostToDevice, st));
+        HGM_HIP(hipMemcpyAsync(dsb, sb, 8 * n_angles, hipMemcpyHostToDevice, st));
+        HGM_HIP(hipMemcpyAsync(geo + 2 * na2, cs, 16 * (size_t)p, hipMemcpyHostToDevice, st));
+        HGM_HIP(hipMemsetAsync(counts, 0, 8 * (n + 1), st));
+        const int g = grid_cap(n);
+        k_fan_backproj<false, double><<<g, BS, 0, st>>>(N, p, n_angles, D, dom, det_offset, dcb, dsb, dcs, tile,
+                                                        super, counts, nullptr, nullptr, nullptr);
+        HGM_HIP(hipGetLastError());
+        HGM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, counts, rp, (int)(n + 1), st));
+        HGM_HIP(hipMalloc(&tmp, tmp_bytes));
+        HGM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, counts, rp, (int)(n + 1), st));
+        int64_t nnz = 0;
+        HGM_HIP(hipMemcpyAsync(&nnz, rp + n, 8, hipMemcpyDeviceToHost, st));
+        HGM_HIP(hipStreamSynchronize(st));
+        M = mat_alloc(c, n, m, nnz, dtype);
+        if (tile > 1 || super > 1) M->row_order = PixOrder{N, tile, super};
+        HGM_HIP(hipMemcpyAsync(M->rp, rp, 8 * (n + 1), hipMemcpyDeviceToDevice, st));
+        if (dtype == HGM_F32)
+            k_fan_backproj<true, float><<<g, BS, 0, st>>>(N, p, n_angles, D, dom, det_offset, dcb, dsb, dcs, tile,
+                                                          super, nullptr, M->rp, M->ci, (float*)M->val);
+        else
+            k_fan_backproj<true, double><<<g, BS, 0, st>>>(N, p, n_angles, D, dom, det_offset, dcb, dsb, dcs, tile,
+                                                           super, nullptr, M->rp, M->ci, (double*)M->val);
         HGM_HIP(hipGetLastError());
         HGM_HIP(hipStreamSynchronize(st));
     } catch (...) {

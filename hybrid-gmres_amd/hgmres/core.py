@@ -334,6 +334,23 @@ class SparseOperator:
                                                      C.byref(h)), ctx)
         return cls._wrap(ctx, h)
 
+    @classmethod
+    def fan_backprojector(cls, N, n_angles, ctx: Context | None = None, R=None, span=None, dtype=L.HGM_F64,
+                          det_offset=None, order="auto"):
+        """Unmatched pixel-driven back-projector B (n x m) of the fan-beam geometry generated on the
+        device, bit-identical to :func:`hgmres.problems.fan_pixel_backprojector`: the ``B != A^T``
+        partner of :meth:`fanbeam` with the same ``R``, ``span`` and ``det_offset``.  ``order``:
+        stored pixel (row) order, as for :meth:`siddon` (pair it with an A of the same order)."""
+        from .problems import DETECTOR_OFFSET, FAN_R
+        ctx = ctx or default_context()
+        off = DETECTOR_OFFSET if det_offset is None else det_offset
+        tile, sup = auto_pixel_order(N) if order == "auto" else ((1, 0) if order == "reference" else order)
+        h = C.c_void_p()
+        _check(L.load().hgm_mat_create_fan_backprojector(ctx.handle, N, n_angles, float(FAN_R if R is None else R),
+                                                         float(0.0 if span is None else span), off, dtype,
+                                                         int(tile), int(sup), C.byref(h)), ctx)
+        return cls._wrap(ctx, h)
+
     def pixel_order(self, which="cols"):
         """(N, tile, super_block) of the stored row/column index order; N = 0: reference order."""
         n_, t_, s_ = C.c_int(), C.c_int(), C.c_int()

@@ -133,6 +133,22 @@ def siddon_projector(N: int, n_angles: int, chunk_elems: int = 1 << 24) -> sp.cs
 FAN_R = 2.0          # source-to-centre distance in units of N (this repository's choice; see fan_geometry)
 
 
+def _fan_tables(N, n_angles, R, span, det_offset):
+    """(p, D, cb, sb, co, so) of the fan geometry: the C-libm cos / sin of the source angles
+    beta_a and of the fan angles omega_d, as the device generators' host side forms them."""
+    p = int(math.ceil(math.sqrt(2.0) * N))
+    if span is None:
+        span = 2.0 * math.asin(1.0 / (math.sqrt(2.0) * R))
+    D = R * N
+    dom = span / p
+    cb = np.array([math.cos(a * (2.0 * math.pi / n_angles)) for a in range(n_angles)])
+    sb = np.array([math.sin(a * (2.0 * math.pi / n_angles)) for a in range(n_angles)])
+    om = [((d - (p - 1) / 2.0) + det_offset) * dom for d in range(p)]
+    co = np.array([math.cos(w) for w in om])
+    so = np.array([math.sin(w) for w in om])
+    return p, D, cb, sb, co, so
+
+
 def fan_geometry(N: int, n_angles: int, R: float = FAN_R, span: float | None = None,
                  det_offset: float = DETECTOR_OFFSET):
     """Fan-beam, curved (equiangular) detector geometry standing in for the CTtype 'fancurved' of
@@ -154,16 +170,7 @@ def fan_geometry(N: int, n_angles: int, R: float = FAN_R, span: float | None = N
       C-libm cos / sin of beta and omega (the same IEEE operations on the host and the device).
     Row index a * p + d (source-angle-major, as the parallel geometry).  Returns
     (p, x0, y0, ux, uy) per ray."""
-    p = int(math.ceil(math.sqrt(2.0) * N))
-    if span is None:
-        span = 2.0 * math.asin(1.0 / (math.sqrt(2.0) * R))
-    D = R * N
-    dom = span / p
-    cb = np.array([math.cos(a * (2.0 * math.pi / n_angles)) for a in range(n_angles)])
-    sb = np.array([math.sin(a * (2.0 * math.pi / n_angles)) for a in range(n_angles)])
-    om = [((d - (p - 1) / 2.0) + det_offset) * dom for d in range(p)]
-    co = np.array([math.cos(w) for w in om])
-    so = np.array([math.sin(w) for w in om])
+    p, D, cb, sb, co, so = _fan_tables(N, n_angles, R, span, det_offset)
     cbr, sbr = np.repeat(cb, p), np.repeat(sb, p)
     cor, sor = np.tile(co, n_angles), np.tile(so, n_angles)
     x0 = D * cbr
@@ -228,6 +235,75 @@ def pixel_driven_backprojector(N: int, n_angles: int) -> sp.csr_matrix:
     return B
 
 
+def fan_pixel_sides(N: int, pix, cb, sb, D: float):
+    """(along, across), each len(pix) x n_angles, of the pixel centres ``pix`` (reference index
+    c*N + r) seen from every source of the fan geometry: with v = centre - source,
+    along = -(v . (cb, sb)) and across = sb vx - cb vy, so that ray d passes the centre on the side
+    s(d) = across * co[d] - along * so[d] = |v| sin(gamma - omega_d).  Every product and sum is
+    rounded on its own, in the order of the device kernel (csrc/ops.hip k_fan_backproj)."""
+    half = N / 2.0
+    pix = np.asarray(pix, dtype=np.int64)
+    xc = ((pix // N) - half) + 0.5
+    yc = ((N - 1 - pix % N) - half) + 0.5
+    vx = xc[:, None] - (D * cb)[None, :]
+    vy = yc[:, None] - (D * sb)[None, :]
+    along = -(vx * cb[None, :] + vy * sb[None, :])
+    across = sb[None, :] * vx - cb[None, :] * vy
+    return along, across
+
+
+def fan_pixel_backprojector(N: int, n_angles: int, R: float = FAN_R, span: float | None = None,
+                            det_offset: float = DETECTOR_OFFSET, chunk_elems: int = 1 << 20) -> sp.csr_matrix:
+    """Unmatched back-projector B (n x m, pixel-major CSR) of the fan-beam geometry
+    (:func:`fan_geometry`, same arguments), pairing with :func:`fanbeam_projector`: for every
+    pixel centre and source, linear interpolation in the fan angle between the two rays that
+    bracket the centre.  With s(d) of :func:`fan_pixel_sides`, d0 is the result of the bisection
+    lo = -1, hi = p; mid = (lo + hi) >> 1; lo = mid if s(mid) >= 0 else hi = mid; a centre outside
+    the fan [omega_0, omega_{p-1}) (d0 < 0 or d0 >= p - 1) gets nothing from that source, the
+    others w1 = s(d0) / (s(d0) - s(d0+1)) at column a*p + d0 + 1 and w0 = 1 - w1 at a*p + d0
+    (where positive), so the weights per (pixel, source) sum to 1: no distance weighting.  This is
+    the repository's own stand-in for PRtomo_mismatched with CTtype 'fancurved'
+    (run_2D_phantom.m:12-15); parity with it is UNPINNED.  Bit-identical to the device generator
+    ``hgm_mat_create_fan_backprojector``.  Chunked over pixels: the largest temporaries are
+    chunk x n_angles."""
+    p, D, cb, sb, co, so = _fan_tables(N, n_angles, R, span, det_offset)
+    n = N * N
+    chunk = max(1, chunk_elems // n_angles)
+    col0 = (np.arange(n_angles, dtype=np.int64) * p)[None, :]
+    counts_all, cols_all, vals_all = [], [], []
+    for p0 in range(0, n, chunk):
+        along, across = fan_pixel_sides(N, np.arange(p0, min(n, p0 + chunk)), cb, sb, D)
+
+        def side(d):
+            return across * co[d] - along * so[d]
+
+        lo = np.full(along.shape, -1, dtype=np.int64)
+        hi = np.full(along.shape, p, dtype=np.int64)
+        while True:
+            act = hi - lo > 1
+            if not act.any():
+                break
+            mid = np.where(act, (lo + hi) >> 1, 0)
+            ge = side(mid) >= 0
+            lo = np.where(act & ge, mid, lo)
+            hi = np.where(act & ~ge, mid, hi)
+        ok = (lo >= 0) & (lo < p - 1)
+        d0 = np.where(ok, lo, 0)
+        s0, s1 = side(d0), side(d0 + 1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w1 = s0 / (s0 - s1)
+        w0 = 1.0 - w1
+        keep = np.stack([ok & (w0 > 0), ok & (w1 > 0)], axis=2)
+        cols = np.stack([col0 + d0, col0 + d0 + 1], axis=2)
+        vals = np.stack([w0, w1], axis=2)
+        counts_all.append(keep.sum(axis=(1, 2)))
+        cols_all.append(cols[keep].astype(np.int32))
+        vals_all.append(vals[keep])
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.concatenate(counts_all), out=indptr[1:])
+    return sp.csr_matrix((np.concatenate(vals_all), np.concatenate(cols_all), indptr), shape=(n, p * n_angles))
+
+
 def shepp_logan(N: int) -> np.ndarray:
     """Modified (Toft) Shepp–Logan phantom on an N x N grid, values in [0, 1].
     Row 0 is the top of the image (y = +1)."""
@@ -276,15 +352,18 @@ class TomoProblem:
 
 def tomo_problem(N: int, n_angles: int, noise: float = 1e-2, seed: int = 0,
                  backprojector: str = "matched", geometry_kind: str = "parallel") -> TomoProblem:
-    """Build (A, B, b, x_true).  ``backprojector`` is ``"matched"`` (B = A^T)
-    or ``"pixel"`` (unmatched pixel-driven B, parallel beam only).  ``geometry_kind``:
-    ``"parallel"`` (Siddon, angles over [0, pi)) or ``"fan"`` (curved-detector fan beam over a
-    full turn, :func:`fan_geometry`)."""
+    """Build (A, B, b, x_true).  ``backprojector`` is ``"matched"`` (B = A^T),
+    ``"pixel"`` (unmatched pixel-driven B, parallel beam only) or ``"fanpixel"`` (unmatched
+    pixel-driven B of the fan beam, :func:`fan_pixel_backprojector`, fan beam only).
+    ``geometry_kind``: ``"parallel"`` (Siddon, angles over [0, pi)) or ``"fan"`` (curved-detector
+    fan beam over a full turn, :func:`fan_geometry`)."""
     if geometry_kind == "fan":
-        if backprojector != "matched":
-            raise ValueError("the fan-beam geometry pairs with the matched back-projector only")
+        if backprojector not in ("matched", "fanpixel"):
+            raise ValueError("the fan-beam geometry pairs with the 'matched' or the 'fanpixel' back-projector")
         A = fanbeam_projector(N, n_angles)
     elif geometry_kind == "parallel":
+        if backprojector == "fanpixel":
+            raise ValueError("the 'fanpixel' back-projector pairs with the fan-beam geometry only")
         A = siddon_projector(N, n_angles)
     else:
         raise ValueError("geometry_kind must be 'parallel' or 'fan'")
@@ -300,8 +379,10 @@ def tomo_problem(N: int, n_angles: int, noise: float = 1e-2, seed: int = 0,
         B.sort_indices()
     elif backprojector == "pixel":
         B = pixel_driven_backprojector(N, n_angles)
+    elif backprojector == "fanpixel":
+        B = fan_pixel_backprojector(N, n_angles)
     else:
-        raise ValueError("backprojector must be 'matched' or 'pixel'")
+        raise ValueError("backprojector must be 'matched', 'pixel' or 'fanpixel'")
     return TomoProblem(N, n_angles, p, A, B, b, b_exact, x_true)
 
 

@@ -312,6 +312,25 @@ HGM_API int hgm_mat_create_fanbeam(hgm_ctx* ctx, int N, int n_angles, double R, 
  * as for hgm_mat_create_siddon_ordered, so B pairs with an operator of the same order. */
 HGM_API int hgm_mat_create_backprojector(hgm_ctx* ctx, int N, int n_angles, double det_offset, int dtype,
                                          int tile, int super_block, hgm_mat** out);
+/* Unmatched pixel-driven back-projector for the fan-beam geometry of hgm_mat_create_fanbeam
+ * (same N, n_angles, R, span, det_offset, same span <= 0 default), generated on the device:
+ * B is N^2 x (p * n_angles), pixel-major, column a*p + d.  For pixel (r, c) (reference row
+ * c*N + r, centre xc = (c - N/2) + 0.5, yc = ((N-1-r) - N/2) + 0.5) and source a, with
+ * cb, sb = cos, sin(a 2 pi / n_angles), co[d], so[d] = cos, sin(omega_d), D = R N:
+ *   vx = xc - D cb, vy = yc - D sb, along = -(vx cb + vy sb), across = sb vx - cb vy,
+ *   s(d) = across co[d] - along so[d]     (= |v| sin(gamma - omega_d), every product and sum
+ *                                           rounded on its own),
+ * d0 = the bisection of s over d (lo = -1, hi = p; mid = (lo+hi)>>1; lo = mid if s(mid) >= 0
+ * else hi = mid).  A pixel outside the fan (d0 < 0 or d0 >= p-1) contributes nothing; otherwise
+ * w1 = s(d0) / (s(d0) - s(d0+1)), w0 = 1 - w1, entries (a*p + d0, w0) and (a*p + d0+1, w1)
+ * where positive, so the weights of a pair sum to 1 (linear interpolation in the fan angle, no
+ * distance weighting).  Bit-identical to hgmres.problems.fan_pixel_backprojector.  It plays the
+ * role of PRtomo_mismatched in run_2D_phantom.m:13-14 for CTtype 'fancurved'; the definition is
+ * this library's own and parity with PRtomo_mismatched is unpinned.  tile / super_block: stored
+ * row (pixel) order, as for hgm_mat_create_backprojector. */
+HGM_API int hgm_mat_create_fan_backprojector(hgm_ctx* ctx, int N, int n_angles, double R, double span,
+                                             double det_offset, int dtype, int tile, int super_block,
+                                             hgm_mat** out);
 /* Stored order of the row (which = 0) or column (which = 1) index space: N = 0 means the
  * reference order. */
 HGM_API int hgm_mat_order(const hgm_mat* mat, int which, int* N, int* tile, int* super_block);
