@@ -1430,6 +1430,93 @@ HGM_API int hgm_gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat
                                      ritz_steps, x, err, res, niters, phi_iter, dphi_iter, mu, ritz_resid));
 }
 
+HGM_API int hgm_svds(hgm_ctx* c, const hgm_mat* A, const hgm_mat* At, const double* b, int steps, int nsv,
+                     double breakdown_tol, const double* X, int64_t ldx, int nx, double* sigma, double* resid,
+                     double* utb, double* VtX, double* U, int64_t ldu, double* V, int64_t ldv, int* steps_done) {
+    // the scalar refusals need no device (and come before any upload); svds() repeats them with messages
+    if (steps < 1 || nsv < 1 || nsv > steps || nx < 0 || nx > 64 || (X && !VtX) || (nx > 0 && !X)) return HGM_E_ARG;
+    if (!c || !A || !At || !sigma || !resid || !utb) return HGM_E_ARG;
+    HGM_SOLVE(c, svds(c, A, At, b, steps, nsv, breakdown_tol, X, ldx, nx, sigma, resid, utb, VtX, U, ldu, V, ldv,
+                      steps_done));
+}
+
+HGM_API int hgm_bidiag_svd(int k, const double* alpha, const double* beta, double* sigma, double* P, double* Q) {
+    if (k < 1 || !alpha || !beta || !sigma) return HGM_E_ARG;
+    dense::bidiag_svd(k, alpha, beta, sigma, P, Q);
+    return HGM_OK;
+}
+
+HGM_API int hgm_basis_project(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq, int nx, const double* X,
+                              int64_t ldx, double* C_host) {
+    if (!c || !Q || !X || !C_host) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_HIP(hipSetDevice(c->device));
+        HGM_REQUIRE(nx >= 1 && k >= 1, "basis_project: at least one column");
+        double* out = c->buf<double>("bp_out", (size_t)k * nx);
+        basis_project(c, rows, k, Q, ldq, nx, X, ldx, out);
+        Reader rd(c);
+        rd.add(C_host, out, sizeof(double) * k * nx);
+        rd.go();
+    });
+    return HGM_OK;
+}
+
+HGM_API int hgm_basis_rotate(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq, int p, const double* Y,
+                             int64_t ldy, double* W, int64_t ldw, double* sumsq_host) {
+    if (!c || !Q || !Y || !W) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_HIP(hipSetDevice(c->device));
+        HGM_REQUIRE(p >= 1, "basis_rotate: at least one column");
+        double* out = sumsq_host ? c->buf<double>("br_out", (size_t)p) : nullptr;
+        basis_rotate(c, rows, k, Q, ldq, p, Y, ldy, W, ldw, out);
+        if (sumsq_host) {
+            Reader rd(c);
+            rd.add(sumsq_host, out, sizeof(double) * p);
+            rd.go();
+        } else {
+            stream_sync(c->stream);
+        }
+    });
+    return HGM_OK;
+}
+
+HGM_API int hgm_basis_project_loop(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq, int nx,
+                                   const double* X, int64_t ldx, double* C_host) {
+    if (!c || !Q || !X || !C_host) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_HIP(hipSetDevice(c->device));
+        HGM_REQUIRE(nx >= 1 && k >= 1 && rows >= 1 && ldq >= rows && ldx >= rows, "basis_project_loop: bad dimensions");
+        double* out = c->buf<double>("bp_out", (size_t)k * nx);
+        hipEvent_t tm;
+        timing_begin(c, KC_BASIS, &tm);
+        // the solvers' one-vector projection (CGS2's Q'w), once per column of X
+        for (int r = 0; r < nx; ++r) multidot<double>(c, rows, k, Q, ldq, X + (int64_t)r * ldx, out + (size_t)r * k);
+        timing_end(c, KC_BASIS, tm, 8.0 * (double)rows * (k + 1.0) * nx);
+        Reader rd(c);
+        rd.add(C_host, out, sizeof(double) * k * nx);
+        rd.go();
+    });
+    return HGM_OK;
+}
+
+HGM_API int hgm_basis_rotate_loop(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq, int p,
+                                  const double* Y, int64_t ldy, double* W, int64_t ldw) {
+    if (!c || !Q || !Y || !W) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_HIP(hipSetDevice(c->device));
+        HGM_REQUIRE(p >= 1 && k >= 1 && rows >= 1 && ldq >= rows && ldy >= k && ldw >= rows,
+                    "basis_rotate_loop: bad dimensions");
+        HGM_REQUIRE(ldq % 2 == 0 && ldw % 2 == 0, "basis_rotate_loop: even leading dimensions (the solvers' gemv)");
+        hipEvent_t tm;
+        timing_begin(c, KC_BASIS, &tm);
+        // the solvers' reconstruction x = Q y, once per column of Y
+        for (int l = 0; l < p; ++l) gemv<double>(c, rows, k, Q, ldq, Y + (int64_t)l * ldy, W + (int64_t)l * ldw, 0);
+        timing_end(c, KC_BASIS, tm, 8.0 * (double)rows * (k + 1.0) * p);
+        stream_sync(c->stream);
+    });
+    return HGM_OK;
+}
+
 HGM_API int hgm_filter_factors(const double* H, int ldh, int k, const double* dK, int lddk, const double* mu,
                                const double* dmu, double lambda, int side, int hybrid, double* phi, double* dphi) {
     if (!H || !dK || !mu || !dmu || !phi || !dphi || k < 1 || ldh < k + 1 || lddk < k) return HGM_E_ARG;

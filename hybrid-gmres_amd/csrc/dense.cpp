@@ -5,6 +5,7 @@
 // §8(a) A6/A8): they are latency-only and far below one kernel launch.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -178,6 +179,86 @@ void svd_values(int n, const double* Min, double* s) {
         s[j] = std::sqrt(t);
     }
     std::sort(s, s + n, [](double a, double b) { return a > b; });
+}
+
+void bidiag_svd(int k, const double* alpha, const double* beta, double* sigma, double* P, double* Q) {
+    // one-sided Jacobi on the columns of G = B V ((k+1) x k), the rotations accumulated in V (k x k):
+    // at convergence G's columns are orthogonal, sigma_j = ||G(:,j)||, P(:,j) = G(:,j) / sigma_j, Q = V
+    const int m = k + 1;
+    std::vector<double> G((size_t)m * k, 0.0), V((size_t)k * k, 0.0);
+    for (int j = 0; j < k; ++j) {
+        AT(G.data(), m, j, j) = alpha[j];
+        AT(G.data(), m, j + 1, j) = beta[j];
+        AT(V.data(), k, j, j) = 1.0;
+    }
+    const double eps = std::numeric_limits<double>::epsilon();
+    for (int sweep = 0; sweep < 80; ++sweep) {
+        double off = 0;
+        for (int p = 0; p < k - 1; ++p)
+            for (int q = p + 1; q < k; ++q) {
+                double a = 0, b = 0, g = 0;
+                for (int i = 0; i < m; ++i) {
+                    const double up = AT(G.data(), m, i, p), uq = AT(G.data(), m, i, q);
+                    a += up * up; b += uq * uq; g += up * uq;
+                }
+                if (g == 0 || std::fabs(g) <= eps * std::sqrt(a * b)) continue;
+                off = std::max(off, std::fabs(g) / std::sqrt(a * b));
+                const double zeta = (b - a) / (2 * g);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1 + zeta * zeta));
+                const double cs = 1 / std::sqrt(1 + t * t), sn = cs * t;
+                for (int i = 0; i < m; ++i) {
+                    const double up = AT(G.data(), m, i, p), uq = AT(G.data(), m, i, q);
+                    AT(G.data(), m, i, p) = cs * up - sn * uq;
+                    AT(G.data(), m, i, q) = sn * up + cs * uq;
+                }
+                for (int i = 0; i < k; ++i) {
+                    const double vp = AT(V.data(), k, i, p), vq = AT(V.data(), k, i, q);
+                    AT(V.data(), k, i, p) = cs * vp - sn * vq;
+                    AT(V.data(), k, i, q) = sn * vp + cs * vq;
+                }
+            }
+        if (off <= eps) break;
+    }
+    std::vector<double> s(k);
+    std::vector<int> ord(k);
+    for (int j = 0; j < k; ++j) {
+        double t = 0;
+        for (int i = 0; i < m; ++i) t += AT(G.data(), m, i, j) * AT(G.data(), m, i, j);
+        s[j] = std::sqrt(t);
+        ord[j] = j;
+    }
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return s[a] > s[b]; });
+    for (int j = 0; j < k; ++j) sigma[j] = s[ord[j]];
+    if (Q)
+        for (int j = 0; j < k; ++j) std::memcpy(Q + (size_t)j * k, &V[(size_t)ord[j] * k], sizeof(double) * k);
+    if (!P) return;
+    for (int j = 0; j < k; ++j) {
+        const double sj = sigma[j];
+        for (int i = 0; i < m; ++i) AT(P, m, i, j) = sj > 0 ? AT(G.data(), m, i, ord[j]) / sj : 0.0;
+    }
+    // a zero singular value leaves its left vector free: complete P to orthonormal columns with the
+    // unit vector that keeps the largest part after two Gram-Schmidt passes against the others
+    for (int j = 0; j < k; ++j) {
+        if (sigma[j] > 0) continue;
+        std::vector<double> best(m, 0.0), w(m);
+        double bestn = -1;
+        for (int e = 0; e < m; ++e) {
+            std::fill(w.begin(), w.end(), 0.0);
+            w[e] = 1.0;
+            for (int pass = 0; pass < 2; ++pass)
+                for (int l = 0; l < k; ++l) {
+                    if (l == j || (sigma[l] <= 0 && l > j)) continue;
+                    double d = 0;
+                    for (int i = 0; i < m; ++i) d += AT(P, m, i, l) * w[i];
+                    for (int i = 0; i < m; ++i) w[i] -= d * AT(P, m, i, l);
+                }
+            double nn = 0;
+            for (int i = 0; i < m; ++i) nn += w[i] * w[i];
+            if (nn > bestn) { bestn = nn; best = w; }
+        }
+        const double nn = std::sqrt(bestn);
+        for (int i = 0; i < m; ++i) AT(P, m, i, j) = best[i] / nn;
+    }
 }
 
 void normal_matrix(const double* H, int ldh, int k, double* G) {

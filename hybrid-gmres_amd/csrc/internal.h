@@ -61,14 +61,14 @@ struct DevBuf {
 };
 
 // Kernel classes timed by hgm_kernel_timing (bench roofline).
-enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_SPMM = 5, KC_GKMV = 6, KC_N = 7 };
+enum KClass { KC_SPMV_A = 0, KC_SPMV_B = 1, KC_MGS = 2, KC_FUSED = 3, KC_PNORM = 4, KC_SPMM = 5, KC_GKMV = 6, KC_BASIS = 7, KC_N = 8 };
 
 struct Timing {
     bool on = false;
     bool paused = false;   // hgm_kernel_timing_pause: armed but not recording
     unsigned mask = 0xffu;   // timed classes
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[KC_N];
-    double bytes[KC_N] = {0, 0, 0, 0, 0, 0, 0};
+    double bytes[KC_N] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::vector<hipEvent_t> pool;
     hipEvent_t get();
     void clear();
@@ -361,6 +361,17 @@ template <typename T>
 void proj_norms(hgm_ctx* c, int64_t rows, int k, const T* V, int64_t ldv, const T* Y, int64_t ldy, int L,
                 const T* t, T* d_out, T* s_out);
 
+// Block products on a basis (basis.hip; hgm_basis_project / hgm_basis_rotate and the post-processing of
+// hgm_svds), each in one pass over Q (rows x k, k <= 256, ldq >= rows), all pointers on the device:
+//   basis_project: C (k x nx, column-major, ld k) = Q' X, in groups of up to 8 columns of X;
+//   basis_rotate:  W (rows x p, p <= 64) = Q Y and, with sumsq_dev, sumsq_dev[l] = sum_i W(i,l)^2.
+// Fixed summation order, no atomics; a column's bits depend on its own data, rows and k only.  Timed
+// under KC_BASIS.
+void basis_project(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq, int nx, const double* X, int64_t ldx,
+                   double* C_dev);
+void basis_rotate(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq, int p, const double* Y, int64_t ldy,
+                  double* W, int64_t ldw, double* sumsq_dev);
+
 // Multi-vector products (spmm.hip; hgm_spmm and the operator of hgm_gmres_bounds_batch).  An interleaved
 // multi-vector of width NV = spmm_width(nvec) in {1, 2, 4, 8} stores element (i, r) at Xi[i*NV + r];
 // slots nvec..NV-1 hold zeros.  spmm: Yi = M Xi with the operator's entries read once for all slots, in
@@ -450,6 +461,12 @@ bool mgs_gram_ok(const hgm_ctx* c, int64_t ldq, int maxit, bool dist);
 // holds v_kk from the previous step's deferral; the dots kernel divides it and writes q_kk.
 template <typename T>
 void cgs2(hgm_ctx* c, int64_t n, T* Q, int64_t ldq, int kk, T* Hcol, bool dist);
+// where cgs2() leaves ||v||^2 of the vector it has just normalised (device; until the context's next mgs /
+// cgs2): sqrt of it is the norm in Hcol[kk+1], bit for bit, so an SpMV epilogue may take it as PendNorm::asq
+template <typename T>
+inline const T* cgs2_sumsq(hgm_ctx* c) {
+    return c->buf<T>("mgs_ss", 4);
+}
 
 // x = Q(:,0:k) * y  (mode 0) ; x = x - Q*y (mode 1)
 template <typename T>
@@ -831,6 +848,10 @@ int gmres_bounds_filter(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const h
                         const double* xt, double tol, int maxit, double lambda, int side, int hybrid,
                         const hgm_mat* dML, const hgm_mat* dMR, int ritz_steps, double* x_out, double* err_out,
                         double* res_out, int* niters, double* phi, double* dphi, double* mu_out, double* ritz_res);
+// svds.cpp: leading singular triplets by Golub-Kahan-Lanczos bidiagonalisation (hgm_svds)
+int svds(hgm_ctx* c, const hgm_mat* A, const hgm_mat* At, const double* b, int steps, int nsv, double breakdown_tol,
+         const double* X, int64_t ldx, int nx, double* sigma, double* resid, double* utb, double* VtX, double* U,
+         int64_t ldu, double* V, int64_t ldv, int* steps_done);
 
 // ---------------- dense host LA (dense.cpp) ----------------
 namespace dense {
@@ -841,6 +862,10 @@ void mldivide_square(int n, const double* M, const double* b, double* x);
 void qr_ls(int m, int n, const double* M, const double* b, double* x);
 // singular values of a square n x n matrix (one-sided Jacobi), descending.
 void svd_values(int n, const double* M, double* s);
+// SVD of the lower bidiagonal B ((k+1) x k: diagonal alpha[0..k), subdiagonal beta[0..k)) = P S Q' by
+// one-sided Jacobi: sigma descending, P (k+1) x k and Q k x k column-major with orthonormal columns
+// (P, Q optional)
+void bidiag_svd(int k, const double* alpha, const double* beta, double* sigma, double* P, double* Q);
 // Projected solves on Hk = H(1:k+1,1:k) (leading dimension ldh), tk = beta e1; G and y are k x k / k.
 // G = Hk'*Hk
 void normal_matrix(const double* H, int ldh, int k, double* G);

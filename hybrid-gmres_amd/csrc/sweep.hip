@@ -6,7 +6,8 @@
 // in ONE pass over V: the rows x L product is a tall-skinny GEMM whose result is squared and summed
 // in the epilogue and never stored.  2kL flops per 8k bytes of V = L/4 flop/B, so from a few tens
 // of columns on the pass is bound by the fp64 issue rate, not by HBM: the products run on the
-// matrix cores (v_mfma_f64_16x16x4_f64), the only fp64 MFMA use of the library.
+// matrix cores (v_mfma_f64_16x16x4_f64).  (basis.hip's block kernels are the library's
+// other fp64 MFMA use.)
 //
 // Layout.  A wave owns tiles of 16 rows.  Per tile it loads the MFMA A operands once, one double per
 // lane and k-quad: lane l holds V[16 tile + (l & 15)][4 q + (l >> 4)] (16 consecutive rows of one

@@ -10,6 +10,8 @@ from .core import SweepResult, gmres_lambda_sweep, proj_norms  # noqa: F401
 from .core import BatchResult, gmres_bounds_batch, spmm  # noqa: F401
 from .core import spmm_pert, gmres_bounds_mismatch, arnoldi_mismatch  # noqa: F401
 from .core import GKBatchResult, gk_batch, mv_axpby_norms  # noqa: F401
+from .core import SvdsResult, svds, empirical_filter_factors, EmpiricalFilterResult  # noqa: F401
+from .core import basis_project, basis_rotate, bidiag_svd  # noqa: F401
 from .core import (  # noqa: F401
     ABgmres_hybrid_bounds,
     ABgmres_nonhybrid_bounds,
@@ -49,4 +51,6 @@ __all__ = [
     "eig", "filter_factors", "ritz", "gmres_lambda_sweep", "proj_norms", "SweepResult",
     "gmres_bounds_batch", "spmm", "BatchResult", "spmm_pert", "gmres_bounds_mismatch", "arnoldi_mismatch",
     "gk_batch", "mv_axpby_norms", "GKBatchResult",
+    "svds", "SvdsResult", "empirical_filter_factors", "EmpiricalFilterResult", "basis_project", "basis_rotate",
+    "bidiag_svd",
 ]

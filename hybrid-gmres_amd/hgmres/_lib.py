@@ -136,6 +136,15 @@ _SIGS = {
     "hgm_gcv_fminbnd": (c_int, [dp, c_int, c_double, c_double, c_double, c_double, c_double, dp, dp]),
     "hgm_gmres_bounds_filter": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, c_double,
                                         c_int, c_int, c_void_p, c_void_p, c_int, dp, dp, dp, P(c_int), dp, dp, dp, dp]),
+    "hgm_svds": (c_int, [c_void_p, c_void_p, c_void_p, dp, c_int, c_int, c_double, dp, c_int64, c_int, dp, dp, dp, dp,
+                         dp, c_int64, dp, c_int64, P(c_int)]),
+    "hgm_bidiag_svd": (c_int, [c_int, dp, dp, dp, dp, dp]),
+    "hgm_basis_project": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, dp]),
+    "hgm_basis_rotate": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                 c_int64, dp]),
+    "hgm_basis_project_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, dp]),
+    "hgm_basis_rotate_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                      c_int64]),
     "hgm_filter_factors": (c_int, [dp, c_int, c_int, dp, c_int, dp, dp, c_double, c_int, c_int, dp, dp]),
     "hgm_ritz": (c_int, [dp, c_int, c_int, c_double, dp, c_int, c_int, dp, dp, dp]),
     "hgm_eig": (c_int, [c_int, dp, dp, dp, dp]),

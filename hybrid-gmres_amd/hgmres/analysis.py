@@ -328,3 +328,34 @@ def error_vs_mismatch_norm(A, B0, E, b, x_true, c_range, *, maxit, tol=1e-6, k_g
         out[f"final_errors_{key}"] = fin
         out[f"niters_{key}"] = nit
     return out
+
+
+def filter_factor_comparison(A, B, b, x_true, *, maxit, tol, lam, DeltaM_AB=None, DeltaM_BA=None, steps, nsv,
+                             ctx=None) -> dict:
+    """The numeric part of ``plot_filter_factors.m:23-40`` (no figures): the four ``*_bounds`` solves with
+    their theoretical filter factors ``phi_final`` (``:23-26``; outputs 5-8 need ``DeltaM_AB`` / ``DeltaM_BA``,
+    else ``phi`` / ``dphi`` are None), and the empirical filter factors of the four solutions on the
+    leading singular triplets of ``A`` (``:30-40``) from ONE :func:`hgmres.core.svds` run started at ``b``
+    with the four solutions as ``X``, in place of ``svd(A,'econ')``.
+
+    Per method ``ab``, ``ba`` (non-hybrid), ``hab``, ``hba`` (hybrid): ``x_*``, ``err_*``, ``res_*``, ``it_*``,
+    ``phi_*`` (``phi_final``), ``dphi_*`` and ``Phi_emp_*`` (``nsv`` values, NaN past the triplets found);
+    plus ``sigma``, ``resid``, ``utb``, ``nconv`` and ``steps_done`` of the triplets."""
+    ctx = ctx or core.default_context()
+    Ao = core.as_operator(A, ctx)
+    Bo = core.as_operator(B, ctx)
+    runs = (("ab", core.ABgmres_nonhybrid_bounds, (), DeltaM_AB),       # :23
+            ("ba", core.BAgmres_nonhybrid_bounds, (), DeltaM_BA),       # :24
+            ("hab", core.ABgmres_hybrid_bounds, (lam,), DeltaM_AB),     # :25
+            ("hba", core.BAgmres_hybrid_bounds, (lam,), DeltaM_BA))     # :26
+    out = {}
+    for name, fn, extra, dm in runs:
+        r = fn(Ao, Bo, b, x_true, tol, maxit, *extra, dm, ctx=ctx)
+        out[f"x_{name}"], out[f"err_{name}"], out[f"res_{name}"], out[f"it_{name}"] = r[:4]
+        out[f"phi_{name}"], out[f"dphi_{name}"] = r[4], r[5]
+    X = np.column_stack([out[f"x_{name}"] for name, *_ in runs])
+    E = core.empirical_filter_factors(Ao, b, X, steps, nsv, ctx=ctx)    # :30-40
+    for j, (name, *_) in enumerate(runs):
+        out[f"Phi_emp_{name}"] = E.Phi[:, j].copy()
+    out.update(sigma=E.sigma, resid=E.resid, utb=E.svds.utb, nconv=E.nconv, steps_done=E.svds.steps_done)
+    return out

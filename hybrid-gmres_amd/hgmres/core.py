@@ -1281,3 +1281,199 @@ def ritz(Hp, h_next, G, nev):
     if rc != L.HGM_OK:
         raise ValueError("hgm_ritz: invalid arguments")
     return mu, dmu, rr
+
+
+# ---- leading singular triplets and empirical filter factors (plot_filter_factors.m:30-40) ----
+def _ld_view(M):
+    """(flat array to upload, leading dimension) of a 2-D array: a column-major view with a leading
+    dimension larger than its row count (``buf[:rows, :]`` of an ``ld x k`` Fortran array) is passed with
+    that leading dimension and its padding rows (except past the last column); anything else is copied
+    to a tight Fortran array."""
+    rows, k = M.shape
+    es = M.itemsize
+    if not (M.strides[0] == es and (k == 1 or (M.strides[1] % es == 0 and M.strides[1] >= rows * es))):
+        M = np.asfortranarray(M)
+    ld = rows if k == 1 else M.strides[1] // es
+    cnt = ld * (k - 1) + rows
+    flat = np.lib.stride_tricks.as_strided(M, shape=(cnt,), strides=(es,)) if ld != rows else M.reshape(-1, order="F")
+    return np.ascontiguousarray(flat), ld
+
+
+class _DevArrays:
+    """Device copies of host arrays for the device-pointer hooks (freed on exit)."""
+
+    def __init__(self, ctx):
+        self.ctx, self.lib, self.ptrs = ctx, L.load(), []
+
+    def alloc(self, count):
+        p = C.c_void_p()
+        _check(self.lib.hgm_dev_alloc(self.ctx.handle, 8 * max(1, int(count)), C.byref(p)), self.ctx)
+        self.ptrs.append(p)
+        return p
+
+    def upload(self, flat):
+        p = self.alloc(flat.size)
+        _check(self.lib.hgm_memcpy_h2d(self.ctx.handle, p, flat.ctypes.data_as(C.c_void_p), 8 * flat.size), self.ctx)
+        return p
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.ptrs:
+            if p.value:
+                self.lib.hgm_dev_free(self.ctx.handle, p)
+        return False
+
+
+def basis_project(Q, X, *, loop=False, ctx=None):
+    """``C = Q.T @ X`` (k x nx) from the device primitive ``hgm_basis_project``: one pass over the basis
+    ``Q`` (rows x k, k <= 256) per group of up to 8 columns of ``X`` (rows x nx).  Column-major views with
+    a larger leading dimension are passed with it (their padding is uploaded and never read).
+    ``loop``: the yardstick ``hgm_basis_project_loop`` instead (the solvers' one-vector projection, one pass
+    over ``Q`` per column of ``X``)."""
+    Q = np.asarray(Q, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64)
+    if Q.ndim != 2 or X.ndim != 2 or X.shape[0] != Q.shape[0]:
+        raise ValueError("basis_project: Q is rows x k and X is rows x nx")
+    rows, k = Q.shape
+    nx = X.shape[1]
+    if rows < 1 or k < 1 or nx < 1:
+        raise ValueError("basis_project: rows, k and nx must be >= 1")
+    ctx = ctx or default_context()
+    qf, ldq = _ld_view(Q)
+    xf, ldx = _ld_view(X)
+    Cm = np.zeros(k * nx)
+    with _DevArrays(ctx) as d:
+        qp, xp = d.upload(qf), d.upload(xf)
+        fn = d.lib.hgm_basis_project_loop if loop else d.lib.hgm_basis_project
+        _check(fn(ctx.handle, rows, k, qp, ldq, nx, xp, ldx, _dp(Cm)), ctx)
+    return Cm.reshape(nx, k).T.copy()
+
+
+def basis_rotate(Q, Y, *, ldw=None, return_sumsq=False, loop=False, ctx=None):
+    """``W = Q @ Y`` (rows x p, p <= 64) from the device primitive ``hgm_basis_rotate``: one pass over the
+    basis ``Q`` (rows x k, k <= 256).  ``ldw``: the leading dimension of the device result (>= rows; its
+    padding is pre-filled with NaN and must come back untouched -- the padded array is returned).
+    ``return_sumsq``: also ``sum_i W[i, l]**2`` as summed on the device.
+    ``loop``: the yardstick ``hgm_basis_rotate_loop`` instead (the solvers' ``x = Q y``, one pass over ``Q`` per
+    column of ``Y``; even leading dimensions, no sums)."""
+    Q = np.asarray(Q, dtype=np.float64)
+    Y = np.asarray(Y, dtype=np.float64)
+    if Q.ndim != 2 or Y.ndim != 2 or Y.shape[0] != Q.shape[1]:
+        raise ValueError("basis_rotate: Q is rows x k and Y is k x p")
+    rows, k = Q.shape
+    p = Y.shape[1]
+    if rows < 1 or k < 1 or p < 1:
+        raise ValueError("basis_rotate: rows, k and p must be >= 1")
+    ldw = rows if ldw is None else int(ldw)
+    if ldw < rows:
+        raise ValueError("basis_rotate: ldw < rows")
+    ctx = ctx or default_context()
+    qf, ldq = _ld_view(Q)
+    yf, ldy = _ld_view(Y)
+    W = np.full(ldw * p, np.nan)
+    ss = np.zeros(p)
+    with _DevArrays(ctx) as d:
+        qp, yp, wp = d.upload(qf), d.upload(yf), d.upload(W)
+        if loop:
+            if return_sumsq:
+                raise ValueError("basis_rotate: the loop form returns no sums")
+            _check(d.lib.hgm_basis_rotate_loop(ctx.handle, rows, k, qp, ldq, p, yp, ldy, wp, ldw), ctx)
+        else:
+            _check(d.lib.hgm_basis_rotate(ctx.handle, rows, k, qp, ldq, p, yp, ldy, wp, ldw,
+                                          _dp(ss) if return_sumsq else None), ctx)
+        _check(d.lib.hgm_memcpy_d2h(ctx.handle, W.ctypes.data_as(C.c_void_p), wp, 8 * W.size), ctx)
+    Wm = W.reshape(p, ldw).T
+    Wm = Wm if ldw != rows else Wm.copy()
+    return (Wm, ss) if return_sumsq else Wm
+
+
+def bidiag_svd(alpha, beta):
+    """``(sigma, P, Q)`` with ``B = P @ diag(sigma) @ Q.T`` for the lower bidiagonal ``B`` ((k+1) x k, diagonal
+    ``alpha``, subdiagonal ``beta``): the host one-sided Jacobi of ``hgm_bidiag_svd``."""
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    k = alpha.size
+    if k < 1 or beta.size != k:
+        raise ValueError("bidiag_svd: alpha and beta have the same length k >= 1")
+    s, Pm, Qm = np.zeros(k), np.zeros((k + 1) * k), np.zeros(k * k)
+    rc = L.load().hgm_bidiag_svd(k, _dp(alpha), _dp(beta), _dp(s), _dp(Pm), _dp(Qm))
+    if rc != L.HGM_OK:
+        raise ValueError("hgm_bidiag_svd: invalid arguments")
+    return s, Pm.reshape(k, k + 1).T.copy(), Qm.reshape(k, k).T.copy()
+
+
+class SvdsResult:
+    """Leading singular triplets from ``svds``: ``sigma``, ``resid`` (= ||A'u - sigma v||), ``utb`` (= u'b >= 0),
+    ``VtX`` (nsv x nx, or None), ``U`` / ``V`` (or None), ``steps_done``.  Entries past
+    ``min(nsv, steps_done)`` are NaN."""
+    __slots__ = ("sigma", "resid", "utb", "VtX", "U", "V", "steps_done")
+
+    def __init__(self, sigma, resid, utb, VtX, U, V, steps_done):
+        self.sigma, self.resid, self.utb, self.VtX, self.U, self.V = sigma, resid, utb, VtX, U, V
+        self.steps_done = steps_done
+
+    def nconv(self, tol=1e-10):
+        """The leading run of triplets with ``resid <= tol * sigma[0]``."""
+        n = 0
+        for r in self.resid:
+            if not (r <= tol * self.sigma[0]):
+                break
+            n += 1
+        return n
+
+
+def svds(A, b, steps, nsv, *, At=None, X=None, return_vectors=False, breakdown_tol=0, ctx=None):
+    """Leading singular triplets of ``A`` by Golub-Kahan-Lanczos bidiagonalisation started at ``b`` with full
+    reorthogonalisation (``hgm_svds``; the ``svd(A,'econ')`` of plot_filter_factors.m:30 restricted to the
+    modes ``b`` excites).  ``b=None``: a fixed deterministic start vector.  ``X`` (n x nx, nx <= 64): also
+    ``VtX = V.T @ X``.  Returns an ``SvdsResult``."""
+    ctx, Ao, Ato = _gkb_ops(A, ctx, At, dtype=A.dtype if isinstance(A, SparseOperator) else L.HGM_F64)
+    m, n = Ao.shape
+    steps, nsv = int(steps), int(nsv)
+    bb = _f64(b, m, "b") if b is not None else None
+    Xf, nx = None, 0
+    if X is not None:
+        Xf = np.asarray(X, dtype=np.float64)
+        if Xf.ndim == 1:
+            Xf = Xf.reshape(-1, 1)
+        if Xf.shape[0] != n:
+            raise ValueError(f"X must have {n} rows")
+        nx = Xf.shape[1]
+        Xf = np.asfortranarray(Xf)
+    ns = max(nsv, 1)
+    sigma, resid, utb = np.zeros(ns), np.zeros(ns), np.zeros(ns)
+    VtX = np.zeros((ns, nx), order="F") if Xf is not None else None
+    U = np.zeros((m, ns), order="F") if return_vectors else None
+    V = np.zeros((n, ns), order="F") if return_vectors else None
+    done = C.c_int(0)
+    _check(L.load().hgm_svds(ctx.handle, Ao._h, Ato._h, _dp(bb) if bb is not None else None, steps, nsv,
+                             float(breakdown_tol), _dp(Xf) if Xf is not None else None, n, nx, _dp(sigma), _dp(resid),
+                             _dp(utb), _dp(VtX) if VtX is not None else None, _dp(U) if U is not None else None, m,
+                             _dp(V) if V is not None else None, n, C.byref(done)), ctx)
+    return SvdsResult(sigma, resid, utb, VtX, U, V, done.value)
+
+
+class EmpiricalFilterResult:
+    """``sigma``, ``Phi`` (nsv x nx), ``resid``, ``nconv`` of ``empirical_filter_factors`` (and the ``svds``
+    result they came from as ``svds``)."""
+    __slots__ = ("sigma", "Phi", "resid", "nconv", "svds")
+
+    def __init__(self, sigma, Phi, resid, nconv, svds_result):
+        self.sigma, self.Phi, self.resid, self.nconv, self.svds = sigma, Phi, resid, nconv, svds_result
+
+    def __iter__(self):
+        return iter((self.sigma, self.Phi, self.resid, self.nconv))
+
+
+def empirical_filter_factors(A, b, X, steps, nsv, *, At=None, breakdown_tol=0, tol=1e-10, ctx=None):
+    """Empirical filter factors ``Phi[i, r] = sigma_i (v_i' x_r) / (u_i' b)`` of the solutions ``X`` (n x nx) on the
+    leading singular triplets from ``svds`` (plot_filter_factors.m:31-40), with the reference's guard
+    ``d(abs(d) < 1e-12) = 1`` on the denominators (:35).  ``nconv``: the leading run with
+    ``resid <= tol * sigma[0]``."""
+    r = svds(A, b, steps, nsv, At=At, X=X, breakdown_tol=breakdown_tol, ctx=ctx)
+    d = r.utb.copy()
+    d[np.abs(d) < 1e-12] = 1.0                                    # :35
+    Phi = r.sigma[:, None] * r.VtX / d[:, None]                   # :31-36
+    return EmpiricalFilterResult(r.sigma, Phi, r.resid, r.nconv(tol), r)

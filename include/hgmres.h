@@ -33,6 +33,9 @@
  *                               gcv_function.m:3-33), every level in lockstep
  *   hgm_gmres_bounds_filter  <- outputs 5-8 of the four *_bounds.m (phi/dphi filter-factor bounds,
  *                               eig(M) of :4-9 replaced by device Ritz pairs)
+ *   hgm_svds                 <- [U,S,V] = svd(A,'econ') and Phi_emp = sigma .* (V'*x) ./ (U'*b) of
+ *                               plot_filter_factors.m:30-40, restricted to the leading modes that b excites
+ *                               (Golub-Kahan-Lanczos started at b; the empirical side of the filter-factor figure)
  *   hgm_mat_create_csc       <- MATLAB sparse (CSC, jc/ir/pr) operand hand-over
  *   hgm_spmv                 <- the `A*v` / `B*u` / `A'*u` mtimes inside every solver
  *
@@ -599,6 +602,54 @@ HGM_API int hgm_ritz(const double* Hp, int ldh, int p, double h_next, const doub
  * V(:,j) +- i V(:,j+1)).  HGM_E_ARG when the QR iteration does not converge. */
 HGM_API int hgm_eig(int n, const double* A, double* wr, double* wi, double* V);
 
+/* ---- leading singular triplets and empirical filter factors (plot_filter_factors.m:30-40) ----
+ * Leading singular triplets of A by Golub-Kahan-Lanczos bidiagonalisation started at b with full
+ * reorthogonalisation (the svd(A,'econ') of plot_filter_factors.m:30, restricted to the modes b excites).
+ *   beta_1 u_1 = b; step j = 1..steps (clipped to min(m, n), at most 255): v^ = A'u_j - beta_j v_{j-1} (on At),
+ *   CGS2 against V(:,1:j-1), alpha_j = ||v^||; u^ = A v_j - alpha_j u_j, CGS2 against U(:,1:j), beta_{j+1} = ||u^||;
+ *   one more half step gives alpha_{k+1}.  On the host B_k = P S Q' (hgm_bidiag_svd), and
+ *     sigma_i = S_ii, resid_i = alpha_{k+1} |P(k+1,i)| (= ||A'u_i - sigma_i v_i||; ||A v_i - sigma_i u_i|| is at
+ *     rounding level), utb_i = u_i'b = beta_1 P(1,i) >= 0 (the sign flips triplet i as a whole),
+ *     VtX = V(:,1:nsv)' X (nsv x nx column-major; through hgm_basis_project), U = U_{k+1} P(:,1:nsv), V = V_k Q(:,1:nsv)
+ *     (through hgm_basis_rotate).  Phi_emp(i,r) = sigma_i VtX(i,r) / utb_i (:31-40).
+ * The start vector selects the modes: a mode with u_i'b = 0 is not found (there the reference divides by its
+ * guard value, :35), and an exactly repeated singular value comes back once, with the projection of b on its
+ * singular subspace.  b == NULL: a fixed deterministic start vector.
+ * A breakdown (alpha or beta <= breakdown_tol x the largest alpha / beta seen so far; <= 0: 1e-12) ends the loop
+ * with *steps_done = the steps completed; it is not an error, and every resid is then 0 (the Krylov space is
+ * invariant).  Entries past min(nsv, *steps_done) are NaN.  X, U and V are host arrays in the reference pixel
+ * order (the bases live in the operator's stored order).
+ * HGM_E_ARG: fp32 operators, parity mode, At NULL or not size(A'), steps < 1, nsv < 1 or nsv > steps, nx < 0 or
+ * nx > 64, X without VtX.  HGM_E_UNSUPPORTED: a communicator or a host all-reduce hook.  HGM_E_NOMEM: the
+ * (m + n)(steps + 1) doubles of the two bases do not fit. */
+HGM_API int hgm_svds(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* At, const double* b /* m, host; NULL: a fixed
+        deterministic start vector */, int steps, int nsv, double breakdown_tol,
+        const double* X /* n x nx host, optional */, int64_t ldx, int nx,
+        double* sigma, double* resid, double* utb /* each nsv */, double* VtX /* nsv x nx, with X */,
+        double* U, int64_t ldu /* m x nsv, optional */, double* V, int64_t ldv /* n x nsv, optional */,
+        int* steps_done);
+/* Host only: SVD of the lower bidiagonal B ((k+1) x k; diagonal alpha, subdiagonal beta) = P S Q' by one-sided
+ * Jacobi: sigma descending, P and Q (optional) column-major with orthonormal columns. */
+HGM_API int hgm_bidiag_svd(int k, const double* alpha /* k */, const double* beta /* k: beta_2..beta_{k+1} */,
+        double* sigma /* k, descending */, double* P /* (k+1) x k */, double* Q /* k x k */);
+/* Device-pointer hooks of the two block kernels on a basis Q (rows x k, k <= 256, ldq >= rows), as hgm_proj_norms
+ * is for the sweep's kernel: C = Q' X (k x nx column-major, to the host; X rows x nx in groups of up to 8 columns,
+ * Q read once per group) and W = Q Y (rows x p, p <= 64, on the device; Y k x p on the device; sumsq_host[l] =
+ * sum_i W(i,l)^2).  Fixed summation order, no atomics: two calls give the same bits, and a column's bits do not
+ * depend on nx / p, on its position or on the other columns.  Padded leading dimensions are never read. */
+HGM_API int hgm_basis_project(hgm_ctx* ctx, int64_t rows, int k, const double* Q_dev, int64_t ldq, int nx,
+        const double* X_dev, int64_t ldx, double* C_host /* k x nx */);
+HGM_API int hgm_basis_rotate(hgm_ctx* ctx, int64_t rows, int k, const double* Q_dev, int64_t ldq, int p,
+        const double* Y_dev, int64_t ldy, double* W_dev, int64_t ldw, double* sumsq_host /* p, optional */);
+/* The same products as a loop of the solvers' one-vector kernels on the same buffers (nx multidot launches /
+ * p gemv launches, each reading Q once): the yardstick the block kernels are measured against
+ * (scripts/basis_micro.py) and a cross-check of them.  The gemv loop needs even leading dimensions and 16-byte
+ * aligned columns, as the solvers' bases have. */
+HGM_API int hgm_basis_project_loop(hgm_ctx* ctx, int64_t rows, int k, const double* Q_dev, int64_t ldq, int nx,
+        const double* X_dev, int64_t ldx, double* C_host);
+HGM_API int hgm_basis_rotate_loop(hgm_ctx* ctx, int64_t rows, int k, const double* Q_dev, int64_t ldq, int p,
+        const double* Y_dev, int64_t ldy, double* W_dev, int64_t ldw);
+
 /* ---- timing hooks used by bench.py ---------------------------------------- */
 /* Average device time (ms) of the named kernel class over the calls since the
  * last reset, measured with HIP events on the context stream.  classes:
@@ -606,7 +657,9 @@ HGM_API int hgm_eig(int n, const double* A, double* wr, double* wi, double* V);
  * 4 = the launches of a hgm_proj_norms / hgm_proj_norms_loop call, 5 = the launches of an hgm_spmm
  * or hgm_spmm_pert product, pack/unpack included (and each operator pass group of hgm_gmres_bounds_batch,
  * hgm_gmres_bounds_mismatch, hgm_arnoldi_mismatch and hgm_gk_batch), 6 = the interleaved multi-vector kernels of
- * hgm_gk_batch and hgm_mv_axpby_norms (recurrences, divisions, sums, packs / unpacks, re-gathers).
+ * hgm_gk_batch and hgm_mv_axpby_norms (recurrences, divisions, sums, packs / unpacks, re-gathers),
+ * 7 = the launches of a basis_project / basis_rotate block pass (hgm_basis_project, hgm_basis_rotate and the
+ * post-processing of hgm_svds; its operator passes and CGS2 keep classes 0 / 1 and 2).
  * enable: 0 = off, 1 = every class, HGM_TIMING_CLASSES(mask) = only the classes whose
  * bit is set (each timed launch carries events, so time only what is read). */
 #define HGM_TIMING_CLASSES(mask) (0x100 | (mask))

@@ -40,6 +40,14 @@
  *        with lambdas(j); an m x 1 Bm with several lambdas is one b shared by every column (a lambda sweep).  x_true is
  *        n x 1 (shared), n x nrhs or []; maxit x nrhs histories (NaN past niters(j)); ar_hist is filled for 'lsmr' only.
  *        Always the production kernels.
+ *   hgmres_mex('svds_gk', A,b,steps,nsv[,X])
+ *        -> [sigma, resid, utb, steps_done, VtX, Phi, nconv, U, V]   the leading singular triplets of A that b excites
+ *        (hgm_svds: Golub-Kahan-Lanczos started at b, full reorthogonalisation) in place of [U,S,V] = svd(A,'econ') of
+ *        plot_filter_factors.m:30, and the empirical filter factors Phi = sigma .* (V'*X) ./ d with the guard
+ *        d(abs(d) < 1e-12) = 1 on d = U'*b (:31-40).  b may be [] (a fixed start vector), X is n x nx (nx <= 64) or []
+ *        (VtX, Phi empty); nsv-long outputs are NaN past min(nsv, steps_done); nconv counts the leading triplets with
+ *        resid <= 1e-10 * sigma(1); U (m x nsv) and V (n x nsv) are formed only when asked for.  Always the production
+ *        kernels.
  *   hgmres_mex('device', d)                      select the HIP device (default 0)
  *   hgmres_mex('parity', 'auto'|'on'|'off')      summation orders (below; default 'auto')
  *
@@ -670,6 +678,60 @@ static void gk_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     if (nlhs > 4) plhs[4] = ni;
 }
 
+/* [sigma, resid, utb, steps_done, VtX, Phi, nconv, U, V] = hgmres_mex('svds_gk', A, b, steps, nsv [, X]).  Every size
+ * is checked before a device is touched. */
+static void svds_gk(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    need_double(prhs[1], "A");
+    const int64_t m = (int64_t)mxGetM(prhs[1]), n = (int64_t)mxGetN(prhs[1]);
+    const double* b = vec(prhs[2], m, "b", 1);
+    const double sv = scalar(prhs[3], "steps"), nv = scalar(prhs[4], "nsv");
+    if (!(sv >= 1) || sv != (double)(int)sv) fail("hgmres:arg", "hgmres: steps must be a positive integer");
+    if (!(nv >= 1) || nv != (double)(int)nv || nv > sv) fail("hgmres:arg", "hgmres: nsv must be an integer in 1..steps");
+    const int steps = (int)sv, nsv = (int)nv;
+    const double* X = NULL;
+    int64_t nx = 0;
+    if (nrhs > 5 && !mxIsEmpty(prhs[5])) {
+        need_double(prhs[5], "X");
+        nx = (int64_t)mxGetN(prhs[5]);
+        if (mxIsSparse(prhs[5]) || (int64_t)mxGetM(prhs[5]) != n || nx < 1 || nx > 64)
+            fail("hgmres:arg", "hgmres: X must be a dense size(A,2) x nx matrix with 1 <= nx <= 64, or []");
+        X = mxGetDoubles(prhs[5]);
+    }
+    hgm_mat* A = op(prhs[1], "A");
+    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
+    hgm_mat* At = transpose_op(A);
+    mxArray* sg = mxCreateDoubleMatrix((mwSize)nsv, 1, mxREAL);
+    mxArray* rs = mxCreateDoubleMatrix((mwSize)nsv, 1, mxREAL);
+    mxArray* ub = mxCreateDoubleMatrix((mwSize)nsv, 1, mxREAL);
+    mxArray* vx = X ? mxCreateDoubleMatrix((mwSize)nsv, (mwSize)nx, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    mxArray* ph = X ? mxCreateDoubleMatrix((mwSize)nsv, (mwSize)nx, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+    mxArray* U = nlhs > 7 ? mxCreateDoubleMatrix((mwSize)m, (mwSize)nsv, mxREAL) : NULL;
+    mxArray* V = nlhs > 8 ? mxCreateDoubleMatrix((mwSize)n, (mwSize)nsv, mxREAL) : NULL;
+    int done = 0;
+    check(hgm_svds(ctx(), A, At, b, steps, nsv, 0.0, X, n > 0 ? n : 1, (int)nx, mxGetDoubles(sg), mxGetDoubles(rs),
+                   mxGetDoubles(ub), X ? mxGetDoubles(vx) : NULL, U ? mxGetDoubles(U) : NULL, m > 0 ? m : 1,
+                   V ? mxGetDoubles(V) : NULL, n > 0 ? n : 1, &done));
+    const double* s = mxGetDoubles(sg);
+    for (int64_t r = 0; r < nx; ++r)                              /* plot_filter_factors.m:31-40 */
+        for (int i = 0; i < nsv; ++i) {
+            double d = mxGetDoubles(ub)[i];
+            if (fabs(d) < 1e-12) d = 1.0;                         /* :35 */
+            mxGetDoubles(ph)[r * nsv + i] = s[i] * mxGetDoubles(vx)[r * nsv + i] / d;
+        }
+    int nconv = 0;
+    while (nconv < nsv && mxGetDoubles(rs)[nconv] <= 1e-10 * s[0]) ++nconv;
+    const double dn = (double)done, dc = (double)nconv;
+    plhs[0] = sg;
+    if (nlhs > 1) plhs[1] = rs;
+    if (nlhs > 2) plhs[2] = ub;
+    if (nlhs > 3) plhs[3] = column(&dn, 1);
+    if (nlhs > 4) plhs[4] = vx;
+    if (nlhs > 5) plhs[5] = ph;
+    if (nlhs > 6) plhs[6] = column(&dc, 1);
+    if (nlhs > 7) plhs[7] = U;
+    if (nlhs > 8) plhs[8] = V;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char fn[32];
     if (nrhs < 1 || !mxIsChar(prhs[0]) || mxGetString(prhs[0], fn, sizeof fn) != 0)
@@ -710,6 +772,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(fn, "gmres_bounds_mismatch")) {
         nargs(nrhs, 10, 11, fn);
         bounds_mismatch(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(fn, "svds_gk")) {
+        nargs(nrhs, 4, 5, fn);
+        svds_gk(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(fn, "gmres_lambda_sweep")) {
         nargs(nrhs, 8, 8, fn);
         lambda_sweep(nlhs, plhs, prhs);
