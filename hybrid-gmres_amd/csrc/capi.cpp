@@ -1111,6 +1111,127 @@ HGM_API int hgm_spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int n
     return HGM_OK;
 }
 
+// ---- the matrix-free dense Gaussian perturbation (gauss.hip) ----
+constexpr int64_t GAUSS_ENTRIES_MAX = (int64_t)1 << 27;
+
+HGM_API int hgm_gauss_create(hgm_ctx* c, int64_t rows, int64_t cols, uint64_t seed, hgm_gauss** out) {
+    if (!c || !out) return HGM_E_ARG;
+    *out = nullptr;
+    HGM_TRY(c, {
+        HGM_REQUIRE(rows >= 1 && cols >= 1, "gauss_create: rows, cols >= 1");
+        hgm_gauss* G = new hgm_gauss;
+        G->ctx = c;
+        G->rows = rows;
+        G->cols = cols;
+        G->seed = seed;
+        *out = G;
+    });
+    return HGM_OK;
+}
+
+HGM_API void hgm_gauss_destroy(hgm_gauss* G) { delete G; }
+
+HGM_API int hgm_gauss_info(const hgm_gauss* G, int64_t* rows, int64_t* cols, uint64_t* seed) {
+    if (!G) return HGM_E_ARG;
+    if (rows) *rows = G->rows;
+    if (cols) *cols = G->cols;
+    if (seed) *seed = G->seed;
+    return HGM_OK;
+}
+
+HGM_API int hgm_gauss_entries(hgm_ctx* c, const hgm_gauss* G, int64_t i0, int64_t ni, int64_t j0, int64_t nj,
+                              double* out, int64_t ldo) {
+    if (!c || !G || !out) return HGM_E_ARG;
+    HGM_TRY(c, {
+        HGM_REQUIRE(i0 >= 0 && j0 >= 0 && ni >= 0 && nj >= 0 && ni <= G->rows - i0 && nj <= G->cols - j0,
+                    "gauss_entries: the block lies outside G");
+        HGM_REQUIRE(ni == 0 || nj <= GAUSS_ENTRIES_MAX / ni, "gauss_entries: at most 2^27 entries per call");
+        HGM_REQUIRE(ldo >= ni, "gauss_entries: ldo >= ni");
+        if (ni > 0 && nj > 0) {
+            HGM_HIP(hipSetDevice(c->device));
+            double* d = c->buf<double>("gauss_block", (size_t)(ni * nj));
+            gauss_entries(c, G, i0, ni, j0, nj, d);
+            HGM_HIP(hipMemcpy2DAsync(out, sizeof(double) * (size_t)ldo, d, sizeof(double) * (size_t)ni,
+                                     sizeof(double) * (size_t)ni, (size_t)nj, hipMemcpyDeviceToHost, c->stream));
+            stream_sync(c->stream);
+        }
+    });
+    return HGM_OK;
+}
+
+HGM_API int hgm_gauss_fro(hgm_ctx* c, const hgm_gauss* G, double* fro) {
+    if (!c || !G || !fro) return HGM_E_ARG;
+    HGM_TRY(c, {
+        if (G->fro < 0.0) {
+            HGM_HIP(hipSetDevice(c->device));
+            G->fro = gauss_fro(c, G);
+        }
+        *fro = G->fro;
+    });
+    return HGM_OK;
+}
+
+// Y = [B0 X +] coefs .* (G X): hgm_spmm's hand-over around the Gaussian product.  B0 (optional) supplies the
+// stored row order of Y and its own stored column order; G reads X in the reference order.
+static void gauss_mm_impl(hgm_ctx* c, const hgm_mat* B0, const hgm_gauss* G, int nvec, const double* coefs,
+                          const double* X, int64_t ldx, double* Y, int64_t ldy, const char* what) {
+    const std::string w(what);
+    HGM_HIP(hipSetDevice(c->device));
+    HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, w + ": 1 <= nvec <= 8");
+    if (B0) {
+        HGM_REQUIRE(B0->dtype == HGM_F64, w + ": fp64 operators only");
+        HGM_REQUIRE(G->rows == B0->rows && G->cols == B0->cols, w + ": G must have B0's shape");
+    }
+    HGM_REQUIRE(ldx >= G->cols && ldy >= G->rows, w + ": ldx >= cols and ldy >= rows");
+    if (coefs)
+        for (int r = 0; r < nvec; ++r) HGM_REQUIRE(std::isfinite(coefs[r]), w + ": every coefficient must be finite");
+    const int NV = spmm_width(nvec);
+    const int64_t rows = G->rows, cols = G->cols;
+    const PixOrder none;
+    const PixOrder& ro = B0 ? B0->row_order : none;
+    const bool xperm = B0 && !B0->col_order.trivial();
+    double* Xi = c->buf<double>("spmm_xi", (size_t)cols * NV);
+    double* Yi = c->buf<double>("spmm_yi", (size_t)rows * NV);
+    double* Xs = xperm ? c->buf<double>("gauss_xs", (size_t)cols * NV) : Xi;   // X in B0's stored column order
+    double* xp = xperm ? c->buf<double>("spmm_x_pix", (size_t)cols * nvec) : nullptr;
+    double* yp = ro.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
+    MvCols src, srcs, dst;
+    for (int r = 0; r < SPMM_MAXV; ++r) src.p[r] = srcs.p[r] = dst.p[r] = nullptr;
+    hipEvent_t tm;
+    timing_begin(c, KC_SPMM, &tm);
+    for (int r = 0; r < nvec; ++r) {
+        src.p[r] = const_cast<double*>(X) + r * ldx;
+        if (xperm) {
+            pix_permute<double>(c, B0->col_order, X + r * ldx, xp + (size_t)r * cols, 0);
+            srcs.p[r] = xp + (size_t)r * cols;
+        }
+        dst.p[r] = yp ? yp + (size_t)r * rows : Y + r * ldy;
+    }
+    mv_pack(c, cols, nvec, src, Xi);
+    if (xperm) mv_pack(c, cols, nvec, srcs, Xs);
+    if (B0) spmm(c, B0, nvec, Xs, Yi);
+    gauss_mm(c, G, ro, nvec, coefs, B0 != nullptr, Xi, Yi);
+    mv_unpack(c, rows, nvec, Yi, dst);
+    if (yp)
+        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, ro, yp + (size_t)r * rows, Y + r * ldy, 1);
+    // G has no stream: the interleaved vectors (and B0's entries)
+    timing_end(c, KC_SPMM, tm, (B0 ? 12.0 * (double)B0->nnz : 0.0) + 8.0 * NV * (rows + cols));
+}
+
+HGM_API int hgm_gauss_mm(hgm_ctx* c, const hgm_gauss* G, int nvec, const double* coefs, const double* X, int64_t ldx,
+                         double* Y, int64_t ldy) {
+    if (!c || !G || !X || !Y) return HGM_E_ARG;
+    HGM_TRY(c, gauss_mm_impl(c, nullptr, G, nvec, coefs, X, ldx, Y, ldy, "gauss_mm"));
+    return HGM_OK;
+}
+
+HGM_API int hgm_spmm_pert_gauss(hgm_ctx* c, const hgm_mat* B0, const hgm_gauss* G, int nvec, const double* coefs,
+                                const double* X, int64_t ldx, double* Y, int64_t ldy) {
+    if (!c || !B0 || !G || !coefs || !X || !Y) return HGM_E_ARG;
+    HGM_TRY(c, gauss_mm_impl(c, B0, G, nvec, coefs, X, ldx, Y, ldy, "spmm_pert_gauss"));
+    return HGM_OK;
+}
+
 // hgm_spmm's hand-over around the interleaved linear-combination kernel (gkmv.hip)
 static void mv_axpby_norms_impl(hgm_ctx* c, int64_t n, int nvec, const double* a, const double* X, int64_t ldx,
                                 const double* b, const double* Y, int64_t ldy, double* Out, int64_t ldo, double* sumsq) {
@@ -1309,6 +1430,16 @@ HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_m
     HGM_SOLVE(c, gmres_bounds_mismatch(c, o, A, B0, E, coefs, ncoef, b, xt, tol, maxit, lambdas, side, hybrid ? 1 : 0,
                                        X, ldx, err, res, niters, col_status));
 }
+HGM_API int hgm_gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0,
+                                            const hgm_gauss* G, const double* coefs, int ncoef, const double* b,
+                                            const double* xt, double tol, int maxit, const double* lambdas, int side,
+                                            int hybrid, double* X, int64_t ldx, double* err, double* res, int* niters,
+                                            int* col_status) {
+    if (!c || !A || !B0 || !G || !coefs || !b || !niters) return HGM_E_ARG;
+    if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
+    HGM_SOLVE(c, gmres_bounds_mismatch_gauss(c, o, A, B0, G, coefs, ncoef, b, xt, tol, maxit, lambdas, side,
+                                             hybrid ? 1 : 0, X, ldx, err, res, niters, col_status));
+}
 HGM_API int hgm_gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
                          int nrhs, const double* xt, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
                          int hybrid, double* X, int64_t ldx, double* err, double* res, double* ar, int* niters) {
@@ -1378,6 +1509,14 @@ HGM_API int hgm_arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0
                                  double breakdown_tol, int orth, double* H, double* beta, int* kdone) {
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
     HGM_SOLVE(c, arnoldi_mismatch(c, A, B0, E, coefs, ncoef, b, k, side, breakdown_tol, orth, H, beta, kdone));
+}
+
+HGM_API int hgm_arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
+                                       const double* coefs, int ncoef, const double* b, int k, int side,
+                                       double breakdown_tol, int orth, double* H, double* beta, int* kdone) {
+    if (!c || !A || !B0 || !G || !coefs || !b) return HGM_E_ARG;
+    if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
+    HGM_SOLVE(c, arnoldi_mismatch_gauss(c, A, B0, G, coefs, ncoef, b, k, side, breakdown_tol, orth, H, beta, kdone));
 }
 
 HGM_API int hgm_gcv_from_H(const double* H, int k, double beta, double lambda, double trace_m, double* gcv) {

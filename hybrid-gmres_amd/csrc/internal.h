@@ -187,6 +187,26 @@ struct PixOrder {
     }
     bool operator!=(const PixOrder& o) const { return !(*this == o); }
 };
+
+// Inverse of ops.hip's pixel_index: stored pixel index of the order (N, tile, super) -> pixel (r, c)
+__host__ __device__ __forceinline__ void pixel_rc(int N, int tile, int super, int64_t idx, int64_t& r, int64_t& c) {
+    const int64_t S = super > 1 ? super : N;
+    const int64_t blk = idx / (S * S), rem = idx % (S * S);
+    const int64_t nb = N / S;
+    const int64_t sc = blk / nb, sr = blk % nb;
+    int64_t rr, cc;
+    if (tile > 1) {
+        const int64_t t = rem / ((int64_t)tile * tile), w = rem % ((int64_t)tile * tile);
+        const int64_t tc = t / (S / tile), tr = t % (S / tile);
+        rr = tr * tile + w % tile;
+        cc = tc * tile + w / tile;
+    } else {
+        rr = rem % S;
+        cc = rem / S;
+    }
+    r = sr * S + rr;
+    c = sc * S + cc;
+}
 }  // namespace hgm
 
 struct hgm_mat {
@@ -238,6 +258,14 @@ struct hgm_mat {
     hgm::FusedPlan* fused = nullptr;
     int64_t fused_key = -1;          // the option tuple the plan was built for (fused.hip fused_key)
     int64_t fused_failed_key = -1;   // the last tuple whose plan was refused (-1: none)
+};
+
+// The matrix-free dense Gaussian perturbation (gauss.hip): shape, seed and the cached norm; no device memory.
+struct hgm_gauss {
+    hgm_ctx* ctx = nullptr;
+    int64_t rows = 0, cols = 0;
+    uint64_t seed = 0;
+    mutable double fro = -1.0;   // cached ||G||_F (hgm_gauss_fro)
 };
 
 namespace hgm {
@@ -394,6 +422,16 @@ void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi);
 bool same_pattern(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E);
 void spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, bool shared, int nvec, const double* coefs,
                const double* Xi, double* Yi);
+
+// Matrix-free Gaussian products (gauss.hip k_gauss_mm): slot r of Yi = [Yi +] (coefs[r] * (G Xi(:,r))) on interleaved
+// multi-vectors (coefs == nullptr: ones), G's entries regenerated from (seed, reference row, column).  Yi's rows
+// are in row_order (a stored pixel order, or trivial), Xi's always in the reference order.  A slot's bits depend
+// on the reference row, G and its own column and coefficient only.  gauss_entries: the ni x nj block at (i0, j0),
+// column-major on the device.  gauss_fro: ||G||_F by one generation pass in a fixed order (one host read).
+void gauss_mm(hgm_ctx* c, const hgm_gauss* G, const PixOrder& row_order, int nvec, const double* coefs, bool accumulate,
+              const double* Xi, double* Yi);
+void gauss_entries(hgm_ctx* c, const hgm_gauss* G, int64_t i0, int64_t ni, int64_t j0, int64_t nj, double* out_dev);
+double gauss_fro(hgm_ctx* c, const hgm_gauss* G);
 
 // Golub-Kahan recurrences on interleaved multi-vectors (gkmv.hip; hgm_mv_axpby_norms and the vector
 // kernels of hgm_gk_batch).  Per-slot coefficients travel by value; a slot's elements and sums depend on
@@ -841,6 +879,14 @@ int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const
 int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs,
                      int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
                      double* beta_out, int* kdone);
+// the same two sweeps with the matrix-free Gaussian G for E (gauss.hip)
+int gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
+                                const double* coefs, int ncoef, const double* b, const double* xt_in, double tol,
+                                int maxit, const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx,
+                                double* err_hist, double* res_hist, int* niters, int* col_status);
+int arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G, const double* coefs,
+                           int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
+                           double* beta_out, int* kdone);
 int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
              int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
              int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, double* ar_hist, int* niters);

@@ -640,25 +640,7 @@ __host__ __device__ __forceinline__ int64_t pixel_index(int N, int tile, int64_t
     return (sc * (N / super) + sr) * (int64_t)super * super + tiled_index(super, tile, r % super, c % super);
 }
 
-// inverse of pixel_index: stored index -> (r, c)
-__host__ __device__ __forceinline__ void pixel_rc(int N, int tile, int super, int64_t idx, int64_t& r, int64_t& c) {
-    const int64_t S = super > 1 ? super : N;
-    const int64_t blk = idx / (S * S), rem = idx % (S * S);
-    const int64_t nb = N / S;
-    const int64_t sc = blk / nb, sr = blk % nb;
-    int64_t rr, cc;
-    if (tile > 1) {
-        const int64_t t = rem / ((int64_t)tile * tile), w = rem % ((int64_t)tile * tile);
-        const int64_t tc = t / (S / tile), tr = t % (S / tile);
-        rr = tr * tile + w % tile;
-        cc = tc * tile + w / tile;
-    } else {
-        rr = rem % S;
-        cc = rem / S;
-    }
-    r = sr * S + rr;
-    c = sc * S + cc;
-}
+// (its inverse, pixel_rc: internal.h)
 
 // reference index p = r + c*N <-> stored index pixel_index(r, c)
 template <typename T>

@@ -1751,7 +1751,8 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
 //    every column (the mismatch sweep);
 //  * the B pass: spmm(B) for every column, or the perturbed product (spmm.hip k_spmm_pert) in which
 //    column j applies B + coefs[j] * E, the coefficients packed with the running columns as they are
-//    regrouped.  The A pass is spmm(A) either way.
+//    regrouped; or, with the matrix-free Gaussian G for E, spmm(B) followed by the accumulating Gaussian
+//    product (gauss.hip k_gauss_mm) with the same packed coefficients.  The A pass is spmm(A) either way.
 // With arnoldi set it is the GCV Arnoldi of gcv_function.m:3-33 per column instead of a solve: no
 // projected solve, no monitors and no kept products; a column leaves at H(k+1,k) < btol (:30) with
 // niters[j] = the steps done (hgm_arnoldi's kdone).
@@ -1760,6 +1761,7 @@ struct Lockstep {
     const double* rhs = nullptr;         // column j's right-hand side: rhs + ldrhs * j (host)
     int64_t ldrhs = 0;                   // 0: one b shared by every column
     const hgm_mat* E = nullptr;          // perturbed B pass (nullptr: spmm(B))
+    const hgm_gauss* G = nullptr;        // ... or the matrix-free Gaussian for E (gauss.hip): spmm(B), then + c_j G
     const double* coefs = nullptr;       // ... column j's coefficient
     bool arnoldi = false;
     double btol = 0.0;                   // arnoldi: the break threshold
@@ -1854,7 +1856,7 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
             ts.p[r] = const_cast<double*>(src(j));
             tm.p[r] = mid(j);
             td.p[r] = dst(j);
-            if (pert) cf[r] = L.coefs[j];
+            if (pert || L.G) cf[r] = L.coefs[j];
         }
         double bytes = 0.0;
         // one pass of the pair: spmm(A), and for B either spmm(B) or the perturbed product
@@ -1866,6 +1868,8 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
             } else {
                 spmm(c, M, nv, in, out);
                 bytes += 12.0 * M->nnz + vec_bytes;
+                // out = (B in) + (c_j * (G in)), G in the reference row order whatever B's stored one is
+                if (M == B && L.G) gauss_mm(c, L.G, B->row_order, nv, cf, true, in, out);
             }
         };
         hipEvent_t tev = nullptr;
@@ -2061,6 +2065,18 @@ void mismatch_guard(const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const
     HGM_REQUIRE(coefs != nullptr, what + ": coefs is required");
     for (int j = 0; j < ncoef; ++j) HGM_REQUIRE(std::isfinite(coefs[j]), what + ": every coefficient must be finite");
 }
+
+// G and the coefficients of a Gaussian mismatch sweep against its B0
+void mismatch_gauss_guard(const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G, const double* coefs, int ncoef,
+                          const std::string& what) {
+    HGM_REQUIRE(G != nullptr, what + ": G is NULL");
+    HGM_REQUIRE(A != B0, what + ": A and B0 must be distinct operators");
+    HGM_REQUIRE(G->rows == B0->rows && G->cols == B0->cols, what + ": G must have B0's shape");
+    HGM_REQUIRE(B0->col_order.trivial(), what + ": B0's columns must be in the reference order");
+    HGM_REQUIRE(ncoef >= 1 && ncoef <= 64, what + ": 1 <= ncoef <= 64");
+    HGM_REQUIRE(coefs != nullptr, what + ": coefs is required");
+    for (int j = 0; j < ncoef; ++j) HGM_REQUIRE(std::isfinite(coefs[j]), what + ": every coefficient must be finite");
+}
 }  // namespace
 
 int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const double* Bm,
@@ -2120,6 +2136,49 @@ int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_
     Lockstep L;
     L.rhs = b;
     L.E = E;
+    L.coefs = coefs;
+    L.arnoldi = true;
+    L.btol = btol;
+    L.beta_out = beta_out;
+    const int st = lockstep_core(c, L, orth, H_out, A, B0, ncoef, nullptr, 0, 0.0, kg, nullptr, side, 0, nullptr, 0,
+                                 nullptr, nullptr, done.data(), nullptr);
+    if (kdone) std::copy(done.begin(), done.end(), kdone);
+    return st;
+}
+
+// The two sweeps above with the matrix-free dense Gaussian G for E (plot_error_vs_mismatch_norm.m:16-17:
+// E = randn(size(A'))): nothing of G is stored, the B pass regenerates it (gauss.hip).
+int gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
+                                const double* coefs, int ncoef, const double* b, const double* xt_in, double tol,
+                                int maxit, const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx,
+                                double* err_hist, double* res_hist, int* niters, int* col_status) {
+    const std::string what = "Gaussian mismatch sweep";
+    lockstep_guard(c, o, A, B0, what);
+    mismatch_gauss_guard(A, B0, G, coefs, ncoef, what);
+    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+    HGM_REQUIRE(b != nullptr && niters != nullptr, "b and niters are required");
+    HGM_REQUIRE(X_out == nullptr || ldx >= A->cols, what + ": ldx >= cols(A)");
+    lockstep_lambdas(lambdas, ncoef, hybrid, what);
+    Lockstep L;
+    L.rhs = b;
+    L.G = G;
+    L.coefs = coefs;
+    return lockstep_core(c, L, o ? o->orth : HGM_MGS, o ? o->H_out : nullptr, A, B0, ncoef, xt_in, 0, tol, maxit,
+                         lambdas, side, hybrid, X_out, ldx, err_hist, res_hist, niters, col_status);
+}
+
+int arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G, const double* coefs,
+                           int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
+                           double* beta_out, int* kdone) {
+    const std::string what = "Gaussian mismatch Arnoldi";
+    lockstep_guard(c, nullptr, A, B0, what);
+    mismatch_gauss_guard(A, B0, G, coefs, ncoef, what);
+    HGM_REQUIRE(kg >= 1, "k must be >= 1");
+    HGM_REQUIRE(b != nullptr, "b is required");
+    std::vector<int> done(ncoef, 0);
+    Lockstep L;
+    L.rhs = b;
+    L.G = G;
     L.coefs = coefs;
     L.arnoldi = true;
     L.btol = btol;

@@ -8,7 +8,7 @@ interface plus the synthetic 2-D tomography problem generator.
 from .core import spmv_ab, fused_plan_info  # noqa: F401
 from .core import SweepResult, gmres_lambda_sweep, proj_norms  # noqa: F401
 from .core import BatchResult, gmres_bounds_batch, spmm  # noqa: F401
-from .core import spmm_pert, gmres_bounds_mismatch, arnoldi_mismatch  # noqa: F401
+from .core import spmm_pert, gmres_bounds_mismatch, arnoldi_mismatch, GaussianPerturbation  # noqa: F401
 from .core import GKBatchResult, gk_batch, mv_axpby_norms  # noqa: F401
 from .core import SvdsResult, svds, empirical_filter_factors, EmpiricalFilterResult  # noqa: F401
 from .core import basis_project, basis_rotate, bidiag_svd  # noqa: F401
@@ -52,5 +52,5 @@ __all__ = [
     "gmres_bounds_batch", "spmm", "BatchResult", "spmm_pert", "gmres_bounds_mismatch", "arnoldi_mismatch",
     "gk_batch", "mv_axpby_norms", "GKBatchResult",
     "svds", "SvdsResult", "empirical_filter_factors", "EmpiricalFilterResult", "basis_project", "basis_rotate",
-    "bidiag_svd",
+    "bidiag_svd", "GaussianPerturbation",
 ]

@@ -99,6 +99,13 @@ _SIGS = {
     "hgm_spmv_ab": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hgm_spmm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64]),
     "hgm_spmm_pert": (c_int, [c_void_p, c_void_p, c_void_p, c_int, dp, c_void_p, c_int64, c_void_p, c_int64]),
+    "hgm_gauss_create": (c_int, [c_void_p, c_int64, c_int64, C.c_uint64, P(c_void_p)]),
+    "hgm_gauss_destroy": (None, [c_void_p]),
+    "hgm_gauss_info": (c_int, [c_void_p, ip64, ip64, P(C.c_uint64)]),
+    "hgm_gauss_entries": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, dp, c_int64]),
+    "hgm_gauss_fro": (c_int, [c_void_p, c_void_p, dp]),
+    "hgm_gauss_mm": (c_int, [c_void_p, c_void_p, c_int, dp, c_void_p, c_int64, c_void_p, c_int64]),
+    "hgm_spmm_pert_gauss": (c_int, [c_void_p, c_void_p, c_void_p, c_int, dp, c_void_p, c_int64, c_void_p, c_int64]),
     "hgm_mv_axpby_norms": (c_int, [c_void_p, c_int64, c_int, dp, c_void_p, c_int64, dp, c_void_p, c_int64, c_void_p, c_int64, dp]),
     "hgm_proj_norms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp, dp]),
     "hgm_proj_norms_loop": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, dp]),
@@ -126,6 +133,11 @@ _SIGS = {
                                           c_int, dp, c_int, c_int, dp, c_int64, dp, dp, P(c_int), P(c_int)]),
     "hgm_arnoldi_mismatch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, dp, c_int, dp, c_int, c_int, c_double, c_int,
                                      dp, dp, P(c_int)]),
+    "hgm_gmres_bounds_mismatch_gauss": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, c_void_p, dp, c_int, dp, dp,
+                                                c_double, c_int, dp, c_int, c_int, dp, c_int64, dp, dp, P(c_int),
+                                                P(c_int)]),
+    "hgm_arnoldi_mismatch_gauss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, dp, c_int, dp, c_int, c_int, c_double,
+                                           c_int, dp, dp, P(c_int)]),
     "hgm_gk_batch": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, c_int64, c_int, dp, c_int64, c_double, c_int, dp,
                              c_int, c_int, dp, c_int64, dp, dp, dp, P(c_int)]),
     "hgm_lsqr_solver_ex": (c_int, [c_void_p, P(hgm_opts), c_void_p, c_void_p, dp, dp, c_double, c_int, dp, dp, dp, P(c_int)]),

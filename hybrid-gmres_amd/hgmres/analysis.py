@@ -254,7 +254,9 @@ def equivalence_vs_noise_level(A, b_exact, x_true, noise_levels, *, maxit, tol=1
 
 
 def _fro(E):
-    """``norm(E, 'fro')`` of a scipy matrix, an array or a device operator."""
+    """``norm(E, 'fro')`` of a scipy matrix, an array, a device operator or a matrix-free Gaussian."""
+    if isinstance(E, core.GaussianPerturbation):
+        return float(E.fro())
     if isinstance(E, core.SparseOperator):
         E = E.to_scipy()
     if hasattr(E, "data") and hasattr(E, "tocsr"):
@@ -269,7 +271,9 @@ def error_vs_mismatch_norm(A, B0, E, b, x_true, c_range, *, maxit, tol=1e-6, k_g
     mismatch levels ``B_pert = B0 + c * E`` for one fixed ``E``, every solver's loop over the levels as ONE
     lockstep solve (:func:`hgmres.core.gmres_bounds_mismatch`) and the GCV Arnoldis of all levels as one
     lockstep Arnoldi per side (:func:`hgmres.core.arnoldi_mismatch`).  No ``B_pert`` is formed or uploaded:
-    ``B0`` and ``E`` are read once per group of up to 8 levels.
+    ``B0`` and ``E`` are read once per group of up to 8 levels.  ``E`` may be a
+    :class:`hgmres.GaussianPerturbation`, the reference's own dense ``E = randn(size(A'))`` (``:16-17``:
+    ``G.normalized()``), which is regenerated on the device and never stored.
 
     ``b`` is the (noisy) right-hand side shared by every level.  The hybrid solvers' lambdas are the GCV
     minimisers of ``:46-50`` (``gcv_fminbnd`` on [1e-9, 1e-1] with TolX 1e-8 on each level's H) unless
@@ -306,7 +310,7 @@ def error_vs_mismatch_norm(A, B0, E, b, x_true, c_range, *, maxit, tol=1e-6, k_g
     ctx = ctx or (A.ctx if isinstance(A, core.SparseOperator) else core.default_context())
     Ao = core.as_operator(A, ctx)                              # uploaded once, reused by every solve
     Bo = core.as_operator(B0, ctx)
-    Eo = core.as_operator(E, ctx)
+    Eo = E if isinstance(E, core.GaussianPerturbation) else core.as_operator(E, ctx)
     chunks = [(lo, min(nl, lo + 64)) for lo in range(0, nl, 64)]            # at most 64 levels per call
     if lambdas is None:                                        # :42-50
         for side in sorted({keys[s][0] for s in solvers if keys[s][1]}):

@@ -507,6 +507,159 @@ def spmm(A: "SparseOperator", X):
     return Y
 
 
+class GaussianPerturbation:
+    """``scale * randn(rows, cols)`` that is never stored: the dense Gaussian back-projector perturbation of
+    ``plot_error_vs_mismatch_norm.m:16`` / ``run_2D_phantom.m:87`` (``E = randn(size(A'))``) as a pure function of
+    ``(seed, i, j)``, regenerated on the device inside every product (``hgm_gauss_*``, csrc/gauss.hip;
+    :func:`hgmres.problems.gaussian_entries` is the host twin).  Takes ``E``'s place in :func:`spmm_pert`,
+    :func:`gmres_bounds_mismatch`, :func:`arnoldi_mismatch` and ``analysis.error_vs_mismatch_norm``.  ``seed`` is
+    64-bit.  ``scale`` multiplies the coefficients on the host (one rounding); the device handle is unscaled."""
+
+    ENTRIES_MAX = 1 << 27
+
+    def __init__(self, rows, cols, seed=0, *, scale=1.0, ctx=None):
+        rows, cols, seed, scale = int(rows), int(cols), int(seed), float(scale)
+        if rows < 1 or cols < 1:
+            raise ValueError(f"GaussianPerturbation: rows, cols >= 1, not ({rows}, {cols})")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("GaussianPerturbation: seed is an unsigned 64-bit integer")
+        if not np.isfinite(scale):
+            raise ValueError("GaussianPerturbation: scale must be finite")
+        self.ctx = ctx or default_context()
+        self.shape, self.seed, self.scale = (rows, cols), seed, scale
+        h = C.c_void_p()
+        _check(L.load().hgm_gauss_create(self.ctx.handle, rows, cols, seed, C.byref(h)), self.ctx)
+        self._handle = h
+        self._root = self          # the instance whose handle (and cached norm) this one uses
+
+    def _with_scale(self, scale):
+        G = object.__new__(GaussianPerturbation)
+        G.ctx, G.shape, G.seed, G.scale = self.ctx, self.shape, self.seed, float(scale)
+        G._root = self._root
+        return G
+
+    @property
+    def _h(self):
+        return self._root._handle
+
+    def close(self):
+        """Frees the handle; an instance made by :meth:`normalized` shares its parent's and frees nothing."""
+        if getattr(self, "_root", None) is self and getattr(self, "_handle", None):
+            L.load().hgm_gauss_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001
+            pass
+
+    def _fro_raw(self):
+        f = C.c_double()
+        _check(L.load().hgm_gauss_fro(self.ctx.handle, self._h, C.byref(f)), self.ctx)
+        return f.value
+
+    def fro(self):
+        """``|scale| * ||G||_F`` (one generation pass on first use, then cached in the handle)."""
+        return abs(self.scale) * self._fro_raw()
+
+    def normalized(self):
+        """The same seed with ``scale = 1 / ||G||_F``: ``E / norm(E, 'fro')`` of
+        ``plot_error_vs_mismatch_norm.m:17``.  Shares this instance's handle."""
+        return self._with_scale(1.0 / self._fro_raw())
+
+    def entries(self, rows=slice(None), cols=slice(None)):
+        """The block ``[rows, cols]`` (unit-step slices) of ``scale * G`` as a host array."""
+        i0, i1, si = rows.indices(self.shape[0])
+        j0, j1, sj = cols.indices(self.shape[1])
+        if si != 1 or sj != 1:
+            raise ValueError("entries: unit-step slices only")
+        ni, nj = max(0, i1 - i0), max(0, j1 - j0)
+        if ni * nj > self.ENTRIES_MAX:
+            raise ValueError(f"entries: at most 2^27 entries per call, not {ni} x {nj}")
+        out = np.empty((ni, nj), order="F")
+        if ni and nj:
+            _check(L.load().hgm_gauss_entries(self.ctx.handle, self._h, i0, ni, j0, nj, _dp(out), ni), self.ctx)
+        return out if self.scale == 1.0 else out * self.scale
+
+    def to_dense(self):
+        if self.shape[0] * self.shape[1] > self.ENTRIES_MAX:
+            raise ValueError(f"to_dense: {self.shape[0]} x {self.shape[1]} is above the 2^27-entry cap")
+        return self.entries()
+
+    def matmat(self, X, coefs=None):
+        """``coefs[r] * scale * (G @ X[:, r])`` for a ``cols x nvec`` host array (``1 <= nvec <= 8``;
+        ``coefs=None``: ones) through ``hgm_gauss_mm``.  A column's bits depend on its own data and coefficient
+        only: not on ``nvec``, its position, the other columns or their coefficients."""
+        m, n = self.shape
+        X, nv = _mm_X(X, n, "matmat")
+        cf = None
+        if coefs is not None or self.scale != 1.0:
+            cf = np.ones(nv) if coefs is None else _coefs(coefs, nv, nv, f"matmat of {nv} vectors")
+            cf = _scaled_coefs(cf, self.scale, "matmat")
+        lib = L.load()
+        return _mm_device(self.ctx, m, n, nv, X,
+                          lambda xd, yd: lib.hgm_gauss_mm(self.ctx.handle, self._h, nv, _dp(cf), xd, n, yd, m))
+
+
+def _scaled_coefs(cf, scale, what):
+    """``cf * scale`` (one rounding), refused when a product is not finite."""
+    with np.errstate(over="ignore"):
+        out = cf if scale == 1.0 else np.ascontiguousarray(cf * scale)
+    if not np.all(np.isfinite(out)):
+        raise ValueError(f"{what}: every coefficient times the scale must be finite")
+    return out
+
+
+def _mm_X(X, n, what):
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    if X.ndim != 2 or X.shape[0] != n:
+        raise ValueError(f"X has shape {X.shape}, expected ({n}, nvec)")
+    nv = X.shape[1]
+    if not 1 <= nv <= 8:
+        raise ValueError(f"{what} takes 1 to 8 vectors, not {nv}")
+    return X, nv
+
+
+def _mm_device(ctx, m, n, nv, X, call):
+    """Upload X (n x nv), run ``call(X_dev, Y_dev)``, download Y (m x nv)."""
+    lib = L.load()
+    Xf = np.asfortranarray(X)
+    Y = np.empty((m, nv), order="F")
+    ptr = [C.c_void_p() for _ in range(2)]
+    try:
+        for p_, k in zip(ptr, (n * nv, m * nv)):
+            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, k), C.byref(p_)), ctx)
+        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
+        _check(call(ptr[0], ptr[1]), ctx)
+        _check(lib.hgm_memcpy_d2h(ctx.handle, Y.ctypes.data_as(C.c_void_p), ptr[1], 8 * m * nv), ctx)
+    finally:
+        for p_ in ptr:
+            if p_.value:
+                lib.hgm_dev_free(ctx.handle, p_)
+    return Y
+
+
+def _spmm_pert_gauss(B0, G, coefs, X):
+    if not isinstance(B0, SparseOperator):
+        raise TypeError("B0 must be a SparseOperator (hgmres.as_operator)")
+    if tuple(G.shape) != tuple(B0.shape):
+        raise ValueError(f"G has shape {G.shape}, expected B0's {B0.shape}")
+    if B0.dtype != L.HGM_F64:
+        raise ValueError("perturbed product: fp64 operators only")
+    m, n = B0.shape
+    X, nv = _mm_X(X, n, "spmm_pert")
+    cf = _scaled_coefs(_coefs(coefs, nv, nv, f"spmm_pert of {nv} vectors"), G.scale, "spmm_pert")
+    ctx = B0.ctx
+    lib = L.load()
+    return _mm_device(ctx, m, n, nv, X,
+                      lambda xd, yd: lib.hgm_spmm_pert_gauss(ctx.handle, B0._h, G._h, nv, _dp(cf), xd, n, yd, m))
+
+
 def _pert_pair(B0, E):
     """The (B0, E) operator pair of a perturbed product, checked on the host."""
     if not isinstance(B0, SparseOperator) or not isinstance(E, SparseOperator):
@@ -531,7 +684,13 @@ def spmm_pert(B0: "SparseOperator", E: "SparseOperator", coefs, X):
     ``hgm_spmm_pert``: column r is the product with ``B0 + coefs[r] * E``, which is never formed, and both
     operators' entries are read once for all columns (spmm.hip).  ``E`` has ``B0``'s shape; when it also has its
     sparsity pattern the index stream and the x gathers are shared.  A column's bits depend on its coefficient
-    only: not on ``nvec``, its position, the other columns or their coefficients."""
+    only: not on ``nvec``, its position, the other columns or their coefficients.
+
+    ``E`` may be a :class:`GaussianPerturbation` (``hgm_spmm_pert_gauss``): column r is then bit for bit
+    ``spmm(B0, X)[:, r] + (coefs[r] * E.scale) * (G @ X[:, r])`` with ``G @ X`` the bits of ``E.matmat``'s unscaled
+    product."""
+    if isinstance(E, GaussianPerturbation):
+        return _spmm_pert_gauss(B0, E, coefs, X)
     _pert_pair(B0, E)
     m, n = B0.shape
     X = np.asarray(X, dtype=np.float64)
@@ -869,6 +1028,8 @@ def _mismatch_args(A, B0, E, coefs, b, what):
 
 def _mismatch_ops(A, B0, E, ctx):
     ctx, Ao, Bo = _ops(A, B0, ctx)
+    if isinstance(E, GaussianPerturbation):
+        return ctx, Ao, Bo, E
     return ctx, Ao, Bo, as_operator(E, ctx, Ao.dtype)
 
 
@@ -881,9 +1042,15 @@ def gmres_bounds_mismatch(A, B0, E, coefs, b, x_true, tol, maxit, side, *, lambd
     uploaded: ``B0`` and ``E`` (``B0``'s shape; its sparsity pattern, or one of its own) are read once per
     group of up to 8 running levels and iteration.  ``side`` is 'ab' or 'ba'; ``lambdas=None`` selects the
     non-hybrid solver; ``x_true`` may be None (the error histories stay NaN).  At most 64 levels per call.
-    Per-column stopping and breakdown as :func:`gmres_bounds_batch`."""
+    Per-column stopping and breakdown as :func:`gmres_bounds_batch`.
+
+    ``E`` may be a :class:`GaussianPerturbation` (``hgm_gmres_bounds_mismatch_gauss``): the dense Gaussian
+    ``E = randn(size(A'))`` of the reference, regenerated inside every B pass and never stored."""
     sd = _side(side)
     m, n, cf, b = _mismatch_args(A, B0, E, coefs, b, "gmres_bounds_mismatch")
+    gauss = isinstance(E, GaussianPerturbation)
+    if gauss:
+        cf = _scaled_coefs(cf, E.scale, "gmres_bounds_mismatch")
     nc = cf.size
     maxit = int(maxit)
     if maxit < 1:
@@ -903,10 +1070,10 @@ def gmres_bounds_mismatch(A, B0, E, coefs, b, x_true, tol, maxit, side, *, lambd
     H = np.zeros((maxit + 1) * maxit * nc) if return_H else None
     o = _opts(orth, H)
     ip = C.POINTER(C.c_int)
-    rc = L.load().hgm_gmres_bounds_mismatch(ctx.handle, C.byref(o), Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), _dp(xt),
-                                            float(tol), maxit, _dp(lam), sd, 0 if lam is None else 1, _dp(X),
-                                            max(n, 1), _dp(err), _dp(res), nit.ctypes.data_as(ip),
-                                            st.ctypes.data_as(ip))
+    fn = L.load().hgm_gmres_bounds_mismatch_gauss if gauss else L.load().hgm_gmres_bounds_mismatch
+    rc = fn(ctx.handle, C.byref(o), Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), _dp(xt), float(tol), maxit, _dp(lam), sd,
+            0 if lam is None else 1, _dp(X), max(n, 1), _dp(err), _dp(res), nit.ctypes.data_as(ip),
+            st.ctypes.data_as(ip))
     if rc != L.HGM_E_NOT_ASSIGNED:
         _check(rc, ctx)
     return BatchResult(X, err, res, nit.astype(int), st.astype(int),
@@ -916,9 +1083,13 @@ def gmres_bounds_mismatch(A, B0, E, coefs, b, x_true, tol, maxit, side, *, lambd
 def arnoldi_mismatch(A, B0, E, coefs, b, k, gcv_type="ba", *, ctx=None, breakdown_tol=1e-12, orth="mgs"):
     """:func:`arnoldi` with the back-projector ``B0 + coefs[j] * E`` for every j in lockstep
     (``hgm_arnoldi_mismatch``; the GCV Arnoldis of ``plot_error_vs_mismatch_norm.m:46-50``): returns
-    (H, beta, kdone) with ``H`` of shape ``ncoef x (k+1) x k`` and ``beta``, ``kdone`` of length ``ncoef``."""
+    (H, beta, kdone) with ``H`` of shape ``ncoef x (k+1) x k`` and ``beta``, ``kdone`` of length ``ncoef``.
+    ``E`` may be a :class:`GaussianPerturbation` (``hgm_arnoldi_mismatch_gauss``)."""
     sd = _side(gcv_type)
     m, n, cf, b = _mismatch_args(A, B0, E, coefs, b, "arnoldi_mismatch")
+    gauss = isinstance(E, GaussianPerturbation)
+    if gauss:
+        cf = _scaled_coefs(cf, E.scale, "arnoldi_mismatch")
     nc = cf.size
     k = int(k)
     if k < 1:
@@ -928,9 +1099,9 @@ def arnoldi_mismatch(A, B0, E, coefs, b, k, gcv_type="ba", *, ctx=None, breakdow
     beta = np.zeros(nc)
     kd = np.zeros(nc, dtype=np.int32)
     o = L.HGM_CGS2 if str(orth).lower() == "cgs2" else L.HGM_MGS
-    _check(L.load().hgm_arnoldi_mismatch(ctx.handle, Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), k, sd,
-                                         float(breakdown_tol), o, _dp(H), _dp(beta),
-                                         kd.ctypes.data_as(C.POINTER(C.c_int))), ctx)
+    fn = L.load().hgm_arnoldi_mismatch_gauss if gauss else L.load().hgm_arnoldi_mismatch
+    _check(fn(ctx.handle, Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), k, sd, float(breakdown_tol), o, _dp(H), _dp(beta),
+              kd.ctypes.data_as(C.POINTER(C.c_int))), ctx)
     return H.reshape(nc, k, k + 1).transpose(0, 2, 1).copy(), beta, kd.astype(int)
 
 

@@ -304,6 +304,72 @@ def fan_pixel_backprojector(N: int, n_angles: int, R: float = FAN_R, span: float
     return sp.csr_matrix((np.concatenate(vals_all), np.concatenate(cols_all), indptr), shape=(n, p * n_angles))
 
 
+# ---------------------------------------------------------------------------
+# The matrix-free dense Gaussian perturbation (csrc/gauss.hip): entry (i, j) of randn(size(A')) as a
+# pure function of (seed, i, j).  This is the host twin of the device generator, step for step.
+# ---------------------------------------------------------------------------
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+GAUSS_ENTRIES_MAX = 1 << 27
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11), vectorised: counter words ``c0..c3`` and key words ``k0, k1``
+    are uint64 arrays (or scalars) holding 32-bit values; returns the four output words as uint64 arrays."""
+    m32 = np.uint64(0xffffffff)
+    sh = np.uint64(32)
+    c0, c1, c2, c3, k0, k1 = np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) & m32
+                                                   for v in (c0, c1, c2, c3, k0, k1)])
+    M0, M1 = np.uint64(PHILOX_M0), np.uint64(PHILOX_M1)
+    W0, W1 = np.uint64(PHILOX_W0), np.uint64(PHILOX_W1)
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2                     # 32 x 32 -> 64 bits, exact in uint64
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & m32, (p0 >> sh) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + W0) & m32, (k1 + W1) & m32
+    return c0, c1, c2, c3
+
+
+def gaussian_entries(rows, cols, seed, i0=0, ni=None, j0=0, nj=None):
+    """The ``ni x nj`` block at (i0, j0) of the ``rows x cols`` standard normal matrix of ``seed`` (64 bits),
+    0-based in the reference order.  Entry (i, j) depends on (seed, i, j) alone: one Philox4x32-10 call with
+    counter (i, j >> 2) gives the four entries of a column quad by Box-Muller, all in fp64:
+    ``u = (a + 0.5) 2^-32``, ``rad = sqrt(-2 log u)``, ``f = b 2^-31``, ``rad cospi(f)`` for even ``j``
+    and ``rad sinpi(f)`` for odd ``j``, with (a, b) words (0, 1) of the call for ``j & 3 < 2``, else (2, 3).
+    ``cospi`` / ``sinpi`` reduce ``f`` exactly to the nearest multiple of 1/2, so every factor has relative
+    error only."""
+    rows, cols, seed = int(rows), int(cols), int(seed) & 0xffffffffffffffff
+    ni = rows - i0 if ni is None else int(ni)
+    nj = cols - j0 if nj is None else int(nj)
+    if rows < 1 or cols < 1:
+        raise ValueError("gaussian_entries: rows, cols >= 1")
+    if i0 < 0 or j0 < 0 or ni < 0 or nj < 0 or i0 + ni > rows or j0 + nj > cols:
+        raise ValueError(f"gaussian_entries: block ({i0}:{i0 + ni}, {j0}:{j0 + nj}) outside {rows} x {cols}")
+    out = np.empty((ni, nj))
+    if ni == 0 or nj == 0:
+        return out
+    q0, q1 = j0 >> 2, (j0 + nj - 1) >> 2
+    i = (np.arange(ni, dtype=np.uint64) + np.uint64(i0))[:, None]
+    q = (np.arange(q1 - q0 + 1, dtype=np.uint64) + np.uint64(q0))[None, :]
+    sh = np.uint64(32)
+    w = philox4x32_10(i, i >> sh, q, q >> sh, np.uint64(seed & 0xffffffff), np.uint64(seed >> 32))
+    quad = np.empty((ni, q1 - q0 + 1, 4))
+    for p in range(2):
+        a, b = w[2 * p], w[2 * p + 1].astype(np.int64)
+        u = (a.astype(np.float64) + 0.5) * 2.0 ** -32
+        rad = np.sqrt(-2.0 * np.log(u))
+        k = (b + (1 << 29)) >> 30                      # nearest multiple of 1/2 to f = b 2^-31
+        r = (b - (k << 30)).astype(np.float64) * 2.0 ** -31     # exact, in [-1/4, 1/4]
+        cr, sr = np.cos(np.pi * r), np.sin(np.pi * r)
+        k &= 3
+        cosv = np.where(k == 0, cr, np.where(k == 1, -sr, np.where(k == 2, -cr, sr)))
+        sinv = np.where(k == 0, sr, np.where(k == 1, cr, np.where(k == 2, -sr, -cr)))
+        quad[:, :, 2 * p] = rad * cosv
+        quad[:, :, 2 * p + 1] = rad * sinv
+    lo = j0 - 4 * q0
+    out[:] = quad.reshape(ni, -1)[:, lo:lo + nj]
+    return out
+
+
 def shepp_logan(N: int) -> np.ndarray:
     """Modified (Toft) Shepp–Logan phantom on an N x N grid, values in [0, 1].
     Row 0 is the top of the image (y = +1)."""

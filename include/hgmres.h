@@ -70,6 +70,7 @@ extern "C" {
 
 typedef struct hgm_ctx hgm_ctx;
 typedef struct hgm_mat hgm_mat;
+typedef struct hgm_gauss hgm_gauss;   /* a matrix-free dense Gaussian matrix (hgm_gauss_create) */
 
 enum hgm_status {
     HGM_OK = 0,
@@ -381,6 +382,35 @@ HGM_API int hgm_spmm(hgm_ctx*, const hgm_mat* A, int nvec, const double* X_dev, 
  * differs from B0's. */
 HGM_API int hgm_spmm_pert(hgm_ctx*, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs_host,
                           const double* X_dev, int64_t ldx, double* Y_dev, int64_t ldy);
+/* ---- the matrix-free dense Gaussian perturbation --------------------------------------------------------
+ * G = randn(rows, cols), the E of plot_error_vs_mismatch_norm.m:16 / run_2D_phantom.m:87 (E = randn(size(A'))),
+ * never stored: entry (i, j), 0-based in the reference order, is a pure function of (seed, i, j).  With
+ * q = j >> 2 and t = j & 3: (w0..w3) = Philox4x32-10(counter (lo i, hi i, lo q, hi q), key (lo seed, hi seed));
+ * (a, b) = (w[2p], w[2p+1]) for p = t >> 1; u = (a + 0.5) 2^-32; rad = sqrt(-2 log u); f = b 2^-31;
+ * g = rad cospi(f) for even t and rad sinpi(f) for odd t, all in fp64.  hgmres/problems.py gaussian_entries is
+ * the host twin.  The handle holds the shape, the seed and a cached norm: no device memory.  rows, cols >= 1. */
+HGM_API int hgm_gauss_create(hgm_ctx*, int64_t rows, int64_t cols, uint64_t seed, hgm_gauss** out);
+HGM_API void hgm_gauss_destroy(hgm_gauss*);
+HGM_API int hgm_gauss_info(const hgm_gauss*, int64_t* rows, int64_t* cols, uint64_t* seed);
+/* The ni x nj block at (i0, j0), column-major into out_host (ldo >= ni).  HGM_E_ARG for a block outside G or
+ * of more than 2^27 entries.  Blocks need not be aligned to the column quads. */
+HGM_API int hgm_gauss_entries(hgm_ctx*, const hgm_gauss*, int64_t i0, int64_t ni, int64_t j0, int64_t nj,
+                              double* out_host, int64_t ldo);
+/* ||G||_F by one generation pass: per-row sums of squares in the product's lane order, then the rows in a
+ * fixed order (no atomics).  Cached in the handle: a repeated call returns the same bits. */
+HGM_API int hgm_gauss_fro(hgm_ctx*, const hgm_gauss*, double* fro);
+/* Y(:,r) = coefs[r] * (G*X(:,r)), r < nvec, 1 <= nvec <= 8; coefs_host NULL: ones.  X is cols x nvec and Y
+ * rows x nvec, column-major device pointers in the reference order (ldx >= cols, ldy >= rows).  Fixed order: a
+ * column's bits depend on G, its own X column and its own coefficient only, not on nvec, its position, or the
+ * other columns and coefficients. */
+HGM_API int hgm_gauss_mm(hgm_ctx*, const hgm_gauss*, int nvec, const double* coefs_host, const double* X_dev,
+                         int64_t ldx, double* Y_dev, int64_t ldy);
+/* hgm_spmm_pert with G for E: Y(:,r) = (B0*X(:,r)) + (coefs[r] * (G*X(:,r))), two roundings, B0*X(:,r) the bits
+ * of hgm_spmm and G*X(:,r) those of hgm_gauss_mm.  G is indexed in the reference order however B0 is stored.
+ * HGM_E_ARG for an fp32 B0, a non-finite coefficient, and a G whose shape differs from B0's. */
+HGM_API int hgm_spmm_pert_gauss(hgm_ctx*, const hgm_mat* B0, const hgm_gauss* G, int nvec,
+                                const double* coefs_host, const double* X_dev, int64_t ldx, double* Y_dev,
+                                int64_t ldy);
 /* Out(:,r) = (a[r]*X(:,r)) + (b[r]*Y(:,r)), r < nvec <= 8, column-major device pointers (ld >= n), coefficients
  * on the host; sumsq_host (optional): nvec values, sum_i Out(i,r)^2 in a fixed order.  Products and sum rounded
  * separately.  A column's bits do not depend on nvec, its position or the other columns.  (The interleaved
@@ -518,6 +548,14 @@ HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx*, const hgm_opts*, const hgm_mat* 
         const hgm_mat* E, const double* coefs, int ncoef, const double* b, const double* x_true, double tol,
         int maxit, const double* lambdas, int side, int hybrid, double* X, int64_t ldx,
         double* error_hist, double* residual_hist, int* niters, int* col_status);
+/* hgm_gmres_bounds_mismatch with the matrix-free Gaussian G for E: column j solves with B = B0 + coefs[j]*G.
+ * The B pass is hgm_spmm's on B0 followed by the accumulating Gaussian product with the group's coefficients
+ * (hgm_spmm_pert_gauss's two roundings).  Every other convention and refusal is hgm_gmres_bounds_mismatch's
+ * (G's shape must be B0's; B0's columns in the reference order). */
+HGM_API int hgm_gmres_bounds_mismatch_gauss(hgm_ctx*, const hgm_opts*, const hgm_mat* A, const hgm_mat* B0,
+        const hgm_gauss* G, const double* coefs, int ncoef, const double* b, const double* x_true, double tol,
+        int maxit, const double* lambdas, int side, int hybrid, double* X, int64_t ldx,
+        double* error_hist, double* residual_hist, int* niters, int* col_status);
 /* nrhs lockstep solves of one Golub-Kahan solver (kind, hybrid) against one operator pair (A, At): column j of
  * every output is what the single solver returns for b = Bm(:,j), x_true = XT(:,j), lambda = lambdas[j]:
  *     kind LSQR, hybrid 0: hgm_lsqr_solver_ex        kind LSQR, hybrid 1: hgm_hybrid_lsqr_solver
@@ -561,6 +599,10 @@ HGM_API int hgm_arnoldi(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B, const 
 HGM_API int hgm_arnoldi_mismatch(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
                                  const double* coefs, int ncoef, const double* b, int k, int side,
                                  double breakdown_tol, int orth, double* H, double* beta, int* kdone);
+/* hgm_arnoldi_mismatch with the matrix-free Gaussian G for E (as hgm_gmres_bounds_mismatch_gauss). */
+HGM_API int hgm_arnoldi_mismatch_gauss(hgm_ctx* ctx, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
+                                       const double* coefs, int ncoef, const double* b, int k, int side,
+                                       double breakdown_tol, int orth, double* H, double* beta, int* kdone);
 /* λ-dependent part of gcv_function.m:35-58 on a cached H (host only). */
 HGM_API int hgm_gcv_from_H(const double* H, int k, double beta, double lambda, double trace_m,
                            double* gcv_val);

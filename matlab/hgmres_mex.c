@@ -29,6 +29,10 @@
  *        batch (hgm_gmres_bounds_batch): column j is the solve of Bm(:,j) with lambdas(j); x_true is n x 1 (shared),
  *        n x nrhs or []; maxit x nrhs histories (NaN past niters(j)); status(j) ~= 0 marks a column whose x was never
  *        assigned (its X column is NaN).  Always the production kernels (the batch has no parity form).
+ *   hgmres_mex('gmres_bounds_mismatch_gauss', side,hybrid, A,B0,seed,scale,coefs,b,x_true,tol,maxit[,lambdas])
+ *        -> [X, error_hist, residual_hist, niters, status]   'gmres_bounds_mismatch' with E = scale*randn(size(B0)) of
+ *        the matrix-free Gaussian generator (hgm_gmres_bounds_mismatch_gauss): E is regenerated on the device inside
+ *        every product and never stored (matlab/gmres_bounds_mismatch_gauss.m)
  *   hgmres_mex('gmres_bounds_mismatch', side,hybrid, A,B0,E,coefs,b,x_true,tol,maxit[,lambdas])
  *        -> [X, error_hist, residual_hist, niters, status]   the loop over the mismatch levels of
  *        plot_error_vs_mismatch_norm.m:23-61 over one {AB,BA}gmres_{hybrid,nonhybrid}_bounds solver as ONE lockstep
@@ -610,6 +614,79 @@ static void bounds_mismatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     if (nlhs > 4) plhs[4] = cs;
 }
 
+/* [X, error_hist, residual_hist, niters, status] = hgmres_mex('gmres_bounds_mismatch_gauss', side, hybrid, A, B0, seed,
+ * scale, coefs, b, x_true, tol, maxit [, lambdas]): 'gmres_bounds_mismatch' with E = scale * randn(size(B0)) of the
+ * matrix-free Gaussian generator (hgm_gauss_create: a pure function of seed, row and column; never stored).  seed is
+ * a non-negative integer below 2^53; the scale multiplies the coefficients here, one rounding.  Everything is checked
+ * before a device is touched. */
+static void bounds_mismatch_gauss(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+    const int side = side_of(prhs[1]);
+    const int hybrid = scalar(prhs[2], "hybrid") != 0.0;
+    need_double(prhs[3], "A");
+    need_double(prhs[4], "B0");
+    const int64_t m = (int64_t)mxGetM(prhs[3]), n = (int64_t)mxGetN(prhs[3]);
+    if ((int64_t)mxGetM(prhs[4]) != n || (int64_t)mxGetN(prhs[4]) != m)
+        fail("hgmres:arg", "hgmres: B0 must be size(A')");
+    if (m < 1 || n < 1) fail("hgmres:arg", "hgmres: the Gaussian perturbation needs a non-empty B0");
+    const double seedv = scalar(prhs[5], "seed");
+    if (!(seedv >= 0.0) || !(seedv <= 9007199254740992.0) || seedv != floor(seedv))
+        fail("hgmres:arg", "hgmres: seed must be a non-negative integer of at most 2^53");
+    const double scale = scalar(prhs[6], "scale");
+    need_double(prhs[7], "coefs");
+    const int64_t nc = (int64_t)mxGetNumberOfElements(prhs[7]);
+    if (mxIsSparse(prhs[7]) || nc < 1 || nc > 64)
+        fail("hgmres:arg", "hgmres: coefs must be a dense vector of 1 to 64 mismatch levels");
+    double* cf = (double*)mxCalloc((size_t)nc, sizeof(double));
+    for (int64_t j = 0; j < nc; ++j) {
+        cf[j] = scale == 1.0 ? mxGetDoubles(prhs[7])[j] : mxGetDoubles(prhs[7])[j] * scale;
+        if (!isfinite(cf[j])) fail("hgmres:arg", "hgmres: every coefficient times the scale must be finite");
+    }
+    const double* b = vec(prhs[8], m, "b", 0);
+    const double* xt = vec(prhs[9], n, "x_true", 1);
+    const double tol = scalar(prhs[10], "tol");
+    const int maxit = maxit_of(prhs[11]);
+    const double* lam = NULL;
+    if (hybrid) {
+        if (nrhs < 13) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per mismatch level)");
+        need_double(prhs[12], "lambdas");
+        if (mxIsSparse(prhs[12]) || (int64_t)mxGetNumberOfElements(prhs[12]) != nc)
+            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per mismatch level");
+        lam = mxGetDoubles(prhs[12]);
+        for (int64_t j = 0; j < nc; ++j)
+            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
+    }
+    hgm_mat* A = op(prhs[3], "A");
+    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
+    hgm_mat* B0 = op(prhs[4], "B0");
+    hgm_gauss* G = NULL;
+    check(hgm_gauss_create(ctx(), n, m, (uint64_t)seedv, &G));
+    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nc, mxREAL);
+    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
+    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
+    int* nit = (int*)mxCalloc((size_t)nc, sizeof(int));
+    int* cst = (int*)mxCalloc((size_t)nc, sizeof(int));
+    for (int64_t i = 0; i < n * nc; ++i) mxGetDoubles(X)[i] = (double)NAN;
+    const int st = hgm_gmres_bounds_mismatch_gauss(ctx(), NULL, A, B0, G, cf, (int)nc, b, xt, tol, maxit, lam, side,
+                                                   hybrid, mxGetDoubles(X), n, mxGetDoubles(e), mxGetDoubles(r), nit,
+                                                   cst);
+    hgm_gauss_destroy(G);
+    if (st != HGM_E_NOT_ASSIGNED) check(st);             /* unassigned columns are reported in status */
+    mxArray* ni = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
+    mxArray* cs = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
+    for (int64_t j = 0; j < nc; ++j) {
+        mxGetDoubles(ni)[j] = (double)nit[j];
+        mxGetDoubles(cs)[j] = (double)cst[j];
+    }
+    mxFree(nit);
+    mxFree(cst);
+    mxFree(cf);
+    plhs[0] = X;
+    if (nlhs > 1) plhs[1] = e;
+    if (nlhs > 2) plhs[2] = r;
+    if (nlhs > 3) plhs[3] = ni;
+    if (nlhs > 4) plhs[4] = cs;
+}
+
 /* [X, error_hist, residual_hist, ar_hist, niters] = hgmres_mex('gk_batch', kind, A, Bm, x_true, tol, maxit [, lambdas]).
  * kind: 'lsqr', 'lsmr', 'hybrid_lsqr' or 'hybrid_lsmr'.  Bm is m x nrhs, or m x 1 with several lambdas (one b shared
  * by every column).  The kind, every size and the lambdas are checked before a device is touched. */
@@ -772,6 +849,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     } else if (!strcmp(fn, "gmres_bounds_mismatch")) {
         nargs(nrhs, 10, 11, fn);
         bounds_mismatch(nlhs, plhs, nrhs, prhs);
+    } else if (!strcmp(fn, "gmres_bounds_mismatch_gauss")) {
+        nargs(nrhs, 11, 12, fn);
+        bounds_mismatch_gauss(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(fn, "svds_gk")) {
         nargs(nrhs, 4, 5, fn);
         svds_gk(nlhs, plhs, nrhs, prhs);
