@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <set>
 #include <vector>
 
@@ -1025,6 +1026,44 @@ HGM_API int hgm_spmv_ab(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const vo
     return HGM_OK;
 }
 
+// the first nvec columns of a column-major matrix (base, leading dimension ld); the other slots are null
+static MvCols mv_cols(const double* base, int64_t ld, int nvec) {
+    MvCols t;
+    for (int r = 0; r < SPMM_MAXV; ++r) t.p[r] = r < nvec ? const_cast<double*>(base) + r * ld : nullptr;
+    return t;
+}
+
+// The hand-over of the multi-vector products (hgm_spmm, hgm_spmm_pert, hgm_gauss_mm, hgm_spmm_pert_gauss): the
+// nvec columns of X are packed into spmm.hip's interleaved layout, product(Xref, Xsto, Yi) runs on the packed
+// buffers and Yi is unpacked into the columns of Y.  A pixel space stored tiled is permuted on the way in / out,
+// as hgm_spmv's vector.  need: the packed inputs the product reads, X in the reference order (Xref), X in the
+// stored column order (Xsto) or both; a product that asks for one of them gets the same buffer twice, and so
+// does one that asks for both where the stored order is the reference order.  bytes: the caller's count for the
+// KC_SPMM bracket.
+enum { MM_X_REF = 1, MM_X_STORED = 2 };
+static void mm_handover(hgm_ctx* c, int64_t rows, int64_t cols, const PixOrder& row_order, const PixOrder& col_order,
+                        int nvec, const double* X, int64_t ldx, double* Y, int64_t ldy, int need, double bytes,
+                        const std::function<void(const double*, const double*, double*)>& product) {
+    const int NV = spmm_width(nvec);
+    const bool xperm = (need & MM_X_STORED) && !col_order.trivial();
+    double* Xi = c->buf<double>("spmm_xi", (size_t)(cols > 0 ? cols : 1) * NV);
+    double* Yi = c->buf<double>("spmm_yi", (size_t)(rows > 0 ? rows : 1) * NV);
+    double* Xs = xperm && (need & MM_X_REF) ? c->buf<double>("gauss_xs", (size_t)cols * NV) : Xi;
+    double* xp = xperm ? c->buf<double>("spmm_x_pix", (size_t)cols * nvec) : nullptr;
+    double* yp = row_order.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
+    hipEvent_t tm;
+    timing_begin(c, KC_SPMM, &tm);
+    if (xperm)
+        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, col_order, X + r * ldx, xp + (size_t)r * cols, 0);
+    if (!xperm || (need & MM_X_REF)) mv_pack(c, cols, nvec, mv_cols(X, ldx, nvec), Xi);
+    if (xperm) mv_pack(c, cols, nvec, mv_cols(xp, cols, nvec), Xs);
+    product(Xi, Xs, Yi);
+    mv_unpack(c, rows, nvec, Yi, yp ? mv_cols(yp, rows, nvec) : mv_cols(Y, ldy, nvec));
+    if (yp)
+        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, row_order, yp + (size_t)r * rows, Y + r * ldy, 1);
+    timing_end(c, KC_SPMM, tm, bytes);
+}
+
 static void spmm_impl(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, int64_t ldx, double* Y, int64_t ldy) {
     HGM_HIP(hipSetDevice(c->device));
     HGM_REQUIRE(A->dtype == HGM_F64, "spmm: fp64 operators only");
@@ -1032,30 +1071,10 @@ static void spmm_impl(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, i
     HGM_REQUIRE(ldx >= A->cols && ldy >= A->rows, "spmm: ldx >= cols and ldy >= rows");
     const int NV = spmm_width(nvec);
     const int64_t rows = A->rows, cols = A->cols;
-    double* Xi = c->buf<double>("spmm_xi", (size_t)(cols > 0 ? cols : 1) * NV);
-    double* Yi = c->buf<double>("spmm_yi", (size_t)(rows > 0 ? rows : 1) * NV);
-    // a pixel space stored tiled: the columns are permuted on the way in / out, as hgm_spmv's vector
-    double* xp = A->col_order.trivial() ? nullptr : c->buf<double>("spmm_x_pix", (size_t)cols * nvec);
-    double* yp = A->row_order.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
-    MvCols src, dst;
-    for (int r = 0; r < SPMM_MAXV; ++r) src.p[r] = dst.p[r] = nullptr;
-    hipEvent_t tm;
-    timing_begin(c, KC_SPMM, &tm);
-    for (int r = 0; r < nvec; ++r) {
-        src.p[r] = const_cast<double*>(X) + r * ldx;
-        if (xp) {
-            pix_permute<double>(c, A->col_order, X + r * ldx, xp + (size_t)r * cols, 0);
-            src.p[r] = xp + (size_t)r * cols;
-        }
-        dst.p[r] = yp ? yp + (size_t)r * rows : Y + r * ldy;
-    }
-    mv_pack(c, cols, nvec, src, Xi);
-    spmm(c, A, nvec, Xi, Yi);
-    mv_unpack(c, rows, nvec, Yi, dst);
-    if (yp)
-        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, A->row_order, yp + (size_t)r * rows, Y + r * ldy, 1);
     // the operator's entries once, the interleaved vectors once each way, the columns once each way
-    timing_end(c, KC_SPMM, tm, 12.0 * (double)A->nnz + 8.0 * (rows + 1) + 8.0 * (2.0 * NV + nvec) * (rows + cols));
+    const double bytes = 12.0 * (double)A->nnz + 8.0 * (rows + 1) + 8.0 * (2.0 * NV + nvec) * (rows + cols);
+    mm_handover(c, rows, cols, A->row_order, A->col_order, nvec, X, ldx, Y, ldy, MM_X_STORED, bytes,
+                [&](const double*, const double* Xs, double* Yi) { spmm(c, A, nvec, Xs, Yi); });
 }
 
 HGM_API int hgm_spmm(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, int64_t ldx, double* Y, int64_t ldy) {
@@ -1064,7 +1083,7 @@ HGM_API int hgm_spmm(hgm_ctx* c, const hgm_mat* A, int nvec, const double* X, in
     return HGM_OK;
 }
 
-// hgm_spmm's hand-over around the perturbed product; B0's stored orders serve both operators
+// the perturbed product; B0's stored orders serve both operators
 static void spmm_pert_impl(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs,
                            const double* X, int64_t ldx, double* Y, int64_t ldy) {
     HGM_HIP(hipSetDevice(c->device));
@@ -1075,33 +1094,13 @@ static void spmm_pert_impl(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int 
                 "spmm_pert: E must be stored in B0's row and column order");
     HGM_REQUIRE(ldx >= B0->cols && ldy >= B0->rows, "spmm_pert: ldx >= cols and ldy >= rows");
     for (int r = 0; r < nvec; ++r) HGM_REQUIRE(std::isfinite(coefs[r]), "spmm_pert: every coefficient must be finite");
-    const int NV = spmm_width(nvec);
     const int64_t rows = B0->rows, cols = B0->cols;
     const bool shared = c->num.pert_shared && same_pattern(c, B0, E);
-    double* Xi = c->buf<double>("spmm_xi", (size_t)(cols > 0 ? cols : 1) * NV);
-    double* Yi = c->buf<double>("spmm_yi", (size_t)(rows > 0 ? rows : 1) * NV);
-    double* xp = B0->col_order.trivial() ? nullptr : c->buf<double>("spmm_x_pix", (size_t)cols * nvec);
-    double* yp = B0->row_order.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
-    MvCols src, dst;
-    for (int r = 0; r < SPMM_MAXV; ++r) src.p[r] = dst.p[r] = nullptr;
-    hipEvent_t tm;
-    timing_begin(c, KC_SPMM, &tm);
-    for (int r = 0; r < nvec; ++r) {
-        src.p[r] = const_cast<double*>(X) + r * ldx;
-        if (xp) {
-            pix_permute<double>(c, B0->col_order, X + r * ldx, xp + (size_t)r * cols, 0);
-            src.p[r] = xp + (size_t)r * cols;
-        }
-        dst.p[r] = yp ? yp + (size_t)r * rows : Y + r * ldy;
-    }
-    mv_pack(c, cols, nvec, src, Xi);
-    spmm_pert(c, B0, E, shared, nvec, coefs, Xi, Yi);
-    mv_unpack(c, rows, nvec, Yi, dst);
-    if (yp)
-        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, B0->row_order, yp + (size_t)r * rows, Y + r * ldy, 1);
     // the kernel's streams (shared: 20 B/entry; general: 12 B/entry of each operator) and the interleaved vectors
-    timing_end(c, KC_SPMM, tm,
-               (shared ? 20.0 * (double)B0->nnz : 12.0 * ((double)B0->nnz + (double)E->nnz)) + 8.0 * NV * (rows + cols));
+    const double bytes = (shared ? 20.0 * (double)B0->nnz : 12.0 * ((double)B0->nnz + (double)E->nnz)) +
+                         8.0 * spmm_width(nvec) * (rows + cols);
+    mm_handover(c, rows, cols, B0->row_order, B0->col_order, nvec, X, ldx, Y, ldy, MM_X_STORED, bytes,
+                [&](const double*, const double* Xs, double* Yi) { spmm_pert(c, B0, E, shared, nvec, coefs, Xs, Yi); });
 }
 
 HGM_API int hgm_spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, int nvec, const double* coefs,
@@ -1171,8 +1170,8 @@ HGM_API int hgm_gauss_fro(hgm_ctx* c, const hgm_gauss* G, double* fro) {
     return HGM_OK;
 }
 
-// Y = [B0 X +] coefs .* (G X): hgm_spmm's hand-over around the Gaussian product.  B0 (optional) supplies the
-// stored row order of Y and its own stored column order; G reads X in the reference order.
+// Y = [B0 X +] coefs .* (G X): the Gaussian product.  B0 (optional) supplies the stored row order of Y and its
+// own stored column order; G reads X in the reference order.
 static void gauss_mm_impl(hgm_ctx* c, const hgm_mat* B0, const hgm_gauss* G, int nvec, const double* coefs,
                           const double* X, int64_t ldx, double* Y, int64_t ldy, const char* what) {
     const std::string w(what);
@@ -1185,37 +1184,16 @@ static void gauss_mm_impl(hgm_ctx* c, const hgm_mat* B0, const hgm_gauss* G, int
     HGM_REQUIRE(ldx >= G->cols && ldy >= G->rows, w + ": ldx >= cols and ldy >= rows");
     if (coefs)
         for (int r = 0; r < nvec; ++r) HGM_REQUIRE(std::isfinite(coefs[r]), w + ": every coefficient must be finite");
-    const int NV = spmm_width(nvec);
     const int64_t rows = G->rows, cols = G->cols;
     const PixOrder none;
     const PixOrder& ro = B0 ? B0->row_order : none;
-    const bool xperm = B0 && !B0->col_order.trivial();
-    double* Xi = c->buf<double>("spmm_xi", (size_t)cols * NV);
-    double* Yi = c->buf<double>("spmm_yi", (size_t)rows * NV);
-    double* Xs = xperm ? c->buf<double>("gauss_xs", (size_t)cols * NV) : Xi;   // X in B0's stored column order
-    double* xp = xperm ? c->buf<double>("spmm_x_pix", (size_t)cols * nvec) : nullptr;
-    double* yp = ro.trivial() ? nullptr : c->buf<double>("spmm_y_pix", (size_t)rows * nvec);
-    MvCols src, srcs, dst;
-    for (int r = 0; r < SPMM_MAXV; ++r) src.p[r] = srcs.p[r] = dst.p[r] = nullptr;
-    hipEvent_t tm;
-    timing_begin(c, KC_SPMM, &tm);
-    for (int r = 0; r < nvec; ++r) {
-        src.p[r] = const_cast<double*>(X) + r * ldx;
-        if (xperm) {
-            pix_permute<double>(c, B0->col_order, X + r * ldx, xp + (size_t)r * cols, 0);
-            srcs.p[r] = xp + (size_t)r * cols;
-        }
-        dst.p[r] = yp ? yp + (size_t)r * rows : Y + r * ldy;
-    }
-    mv_pack(c, cols, nvec, src, Xi);
-    if (xperm) mv_pack(c, cols, nvec, srcs, Xs);
-    if (B0) spmm(c, B0, nvec, Xs, Yi);
-    gauss_mm(c, G, ro, nvec, coefs, B0 != nullptr, Xi, Yi);
-    mv_unpack(c, rows, nvec, Yi, dst);
-    if (yp)
-        for (int r = 0; r < nvec; ++r) pix_permute<double>(c, ro, yp + (size_t)r * rows, Y + r * ldy, 1);
     // G has no stream: the interleaved vectors (and B0's entries)
-    timing_end(c, KC_SPMM, tm, (B0 ? 12.0 * (double)B0->nnz : 0.0) + 8.0 * NV * (rows + cols));
+    const double bytes = (B0 ? 12.0 * (double)B0->nnz : 0.0) + 8.0 * spmm_width(nvec) * (rows + cols);
+    mm_handover(c, rows, cols, ro, B0 ? B0->col_order : none, nvec, X, ldx, Y, ldy,
+                B0 ? MM_X_REF | MM_X_STORED : MM_X_REF, bytes, [&](const double* Xref, const double* Xs, double* Yi) {
+                    if (B0) spmm(c, B0, nvec, Xs, Yi);
+                    gauss_mm(c, G, ro, nvec, coefs, B0 != nullptr, Xref, Yi);
+                });
 }
 
 HGM_API int hgm_gauss_mm(hgm_ctx* c, const hgm_gauss* G, int nvec, const double* coefs, const double* X, int64_t ldx,
@@ -1243,12 +1221,8 @@ static void mv_axpby_norms_impl(hgm_ctx* c, int64_t n, int nvec, const double* a
     double* Xi = c->buf<double>("gkmv_xi", (size_t)(n > 0 ? n : 1) * NV);
     double* Yi = c->buf<double>("gkmv_yi", (size_t)(n > 0 ? n : 1) * NV);
     double* sums = c->buf<double>("gkmv_sums", SPMM_MAXV);
-    MvCols sx, sy, so;
     MvLin L;
     for (int r = 0; r < SPMM_MAXV; ++r) {
-        sx.p[r] = r < nvec ? const_cast<double*>(X) + r * ldx : nullptr;
-        sy.p[r] = r < nvec ? const_cast<double*>(Y) + r * ldy : nullptr;
-        so.p[r] = r < nvec ? Out + r * ldo : nullptr;
         L.a.c[r] = r < nvec ? a[r] : 0.0;
         L.b.c[r] = r < nvec ? b[r] : 0.0;
     }
@@ -1259,10 +1233,10 @@ static void mv_axpby_norms_impl(hgm_ctx* c, int64_t n, int nvec, const double* a
     L.sums = sums;
     hipEvent_t tm;
     timing_begin(c, KC_GKMV, &tm);
-    mv_pack(c, n, nvec, sx, Xi);
-    mv_pack(c, n, nvec, sy, Yi);
+    mv_pack(c, n, nvec, mv_cols(X, ldx, nvec), Xi);
+    mv_pack(c, n, nvec, mv_cols(Y, ldy, nvec), Yi);
     mv_lin(c, n, nvec, L);
-    mv_unpack(c, n, nvec, Xi, so);
+    mv_unpack(c, n, nvec, Xi, mv_cols(Out, ldo, nvec));
     timing_end(c, KC_GKMV, tm, 8.0 * (double)n * (3.0 * nvec + 5.0 * NV));
     if (sumsq) {
         Reader rd(c);
@@ -1427,8 +1401,8 @@ HGM_API int hgm_gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_m
                                       int hybrid, double* X, int64_t ldx, double* err, double* res, int* niters,
                                       int* col_status) {
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
-    HGM_SOLVE(c, gmres_bounds_mismatch(c, o, A, B0, E, coefs, ncoef, b, xt, tol, maxit, lambdas, side, hybrid ? 1 : 0,
-                                       X, ldx, err, res, niters, col_status));
+    HGM_SOLVE(c, gmres_bounds_mismatch(c, o, A, B0, Perturbation{E, nullptr, coefs, ncoef}, b, xt, tol, maxit, lambdas, side,
+                                       hybrid ? 1 : 0, X, ldx, err, res, niters, col_status));
 }
 HGM_API int hgm_gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0,
                                             const hgm_gauss* G, const double* coefs, int ncoef, const double* b,
@@ -1437,8 +1411,8 @@ HGM_API int hgm_gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const
                                             int* col_status) {
     if (!c || !A || !B0 || !G || !coefs || !b || !niters) return HGM_E_ARG;
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
-    HGM_SOLVE(c, gmres_bounds_mismatch_gauss(c, o, A, B0, G, coefs, ncoef, b, xt, tol, maxit, lambdas, side,
-                                             hybrid ? 1 : 0, X, ldx, err, res, niters, col_status));
+    HGM_SOLVE(c, gmres_bounds_mismatch(c, o, A, B0, Perturbation{nullptr, G, coefs, ncoef}, b, xt, tol, maxit, lambdas, side,
+                                       hybrid ? 1 : 0, X, ldx, err, res, niters, col_status));
 }
 HGM_API int hgm_gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
                          int nrhs, const double* xt, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
@@ -1508,7 +1482,8 @@ HGM_API int hgm_arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0
                                  const double* coefs, int ncoef, const double* b, int k, int side,
                                  double breakdown_tol, int orth, double* H, double* beta, int* kdone) {
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
-    HGM_SOLVE(c, arnoldi_mismatch(c, A, B0, E, coefs, ncoef, b, k, side, breakdown_tol, orth, H, beta, kdone));
+    HGM_SOLVE(c, arnoldi_mismatch(c, A, B0, Perturbation{E, nullptr, coefs, ncoef}, b, k, side, breakdown_tol, orth, H,
+                                  beta, kdone));
 }
 
 HGM_API int hgm_arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
@@ -1516,7 +1491,8 @@ HGM_API int hgm_arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_m
                                        double breakdown_tol, int orth, double* H, double* beta, int* kdone) {
     if (!c || !A || !B0 || !G || !coefs || !b) return HGM_E_ARG;
     if (side != HGM_SIDE_AB && side != HGM_SIDE_BA) return HGM_E_ARG;
-    HGM_SOLVE(c, arnoldi_mismatch_gauss(c, A, B0, G, coefs, ncoef, b, k, side, breakdown_tol, orth, H, beta, kdone));
+    HGM_SOLVE(c, arnoldi_mismatch(c, A, B0, Perturbation{nullptr, G, coefs, ncoef}, b, k, side, breakdown_tol, orth, H,
+                                  beta, kdone));
 }
 
 HGM_API int hgm_gcv_from_H(const double* H, int k, double beta, double lambda, double trace_m, double* gcv) {

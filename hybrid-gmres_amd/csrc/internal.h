@@ -872,21 +872,20 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                        int64_t ldb, int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit,
                        const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
                        double* res_hist, int* niters, int* col_status);
-int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
-                          const double* coefs, int ncoef, const double* b, const double* xt_in, double tol, int maxit,
-                          const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
-                          double* res_hist, int* niters, int* col_status);
-int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs,
-                     int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
-                     double* beta_out, int* kdone);
-// the same two sweeps with the matrix-free Gaussian G for E (gauss.hip)
-int gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
-                                const double* coefs, int ncoef, const double* b, const double* xt_in, double tol,
-                                int maxit, const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx,
-                                double* err_hist, double* res_hist, int* niters, int* col_status);
-int arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G, const double* coefs,
-                           int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
-                           double* beta_out, int* kdone);
+// the perturbation of a mismatch sweep: column j applies B0 + coefs[j] * E, E a stored sparse operator or,
+// with G, the matrix-free Gaussian (gauss.hip); exactly one of the two is set
+struct Perturbation {
+    const hgm_mat* E = nullptr;
+    const hgm_gauss* G = nullptr;
+    const double* coefs = nullptr;   // ncoef of them, one per column
+    int ncoef = 0;
+};
+int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const Perturbation& P,
+                          const double* b, const double* xt_in, double tol, int maxit, const double* lambdas, int side,
+                          int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, int* niters,
+                          int* col_status);
+int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const Perturbation& P, const double* b, int kg,
+                     int side, double btol, int orth, double* H_out, double* beta_out, int* kdone);
 int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, const double* Bm, int64_t ldb,
              int nrhs, const double* xt_in, int64_t ldxt, double tol, int maxit, const double* lambdas, int kind,
              int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, double* ar_hist, int* niters);

@@ -1757,12 +1757,90 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
 // projected solve, no monitors and no kept products; a column leaves at H(k+1,k) < btol (:30) with
 // niters[j] = the steps done (hgm_arnoldi's kdone).
 namespace {
+// The column batch of a lockstep solve (lockstep_core and gk_batch): the right-hand sides, x_true and the
+// iterates of nrhs columns as device slabs with a constant column stride, and the way in and out.
+struct ColBatch {
+    // column j of a slab; one shared column serves every j
+    struct Cols {
+        double* p = nullptr;
+        int64_t ld = 0;
+        bool shared = false;
+        double* operator()(int j) const { return p + (size_t)ld * (shared ? 0 : j); }
+    };
+    Cols bj, xtj, xj;
+    int nrhs = 0;
+    int64_t n = 0;
+    PixOrder po;
+
+    // the requirements of the entry points that take column matrices; shared_b: ldb == 0 is one b for every column
+    static void require(const std::string& what, const hgm_mat* A, const double* Bm, int64_t ldb, bool shared_b,
+                        int nrhs, const double* xt_in, int64_t ldxt, int maxit, const double* X_out, int64_t ldx,
+                        const int* niters) {
+        HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, what + ": 1 <= nrhs <= 64");
+        HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
+        HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
+        const int64_t m = A->rows, n = A->cols;
+        if (shared_b) HGM_REQUIRE(ldb == 0 || ldb >= m, what + ": ldb is 0 (one shared b) or >= rows(A)");
+        else HGM_REQUIRE(ldb >= m, what + ": ldb >= rows(A)");
+        HGM_REQUIRE(X_out == nullptr || ldx >= n, what + ": ldx >= cols(A)");
+        HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, what + ": ldxt is 0 (one shared x_true) or >= cols(A)");
+    }
+
+    // Empty outputs (histories NaN, niters 0), then b (ldrhs == 0: one shared by every column) and x_true (none,
+    // ldxt == 0: one shared, or one per column; given in the reference order, kept in the stored pixel order po)
+    // on the device.  Workspace names start with pre.  zero_xt: without an x_true the one column is zeroed.
+    ColBatch(hgm_ctx* c, const std::string& pre, const hgm_mat* A, const PixOrder& order, int ncols, const double* rhs,
+             int64_t ldrhs, const double* xt_in, int64_t ldxt, bool zero_xt, int maxit,
+             std::initializer_list<double*> hists, int* niters)
+        : nrhs(ncols), n(A->cols), po(order) {
+        const int64_t m = A->rows;
+        const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
+        for (double* h : hists)
+            if (h) std::fill(h, h + (size_t)maxit * nrhs, std::numeric_limits<double>::quiet_NaN());
+        for (int j = 0; j < nrhs; ++j) niters[j] = 0;
+        const int nb_cols = ldrhs == 0 ? 1 : nrhs;
+        const int nxt_cols = xt_in && ldxt != 0 ? nrhs : 1;
+        bj = {c->buf<double>((pre + "ball").c_str(), (size_t)ldm * nb_cols), ldm, nb_cols == 1};
+        xtj = {c->buf<double>((pre + "xtall").c_str(), (size_t)ldn * nxt_cols), ldn, nxt_cols == 1};
+        xj = {c->buf<double>((pre + "xall").c_str(), (size_t)ldn * nrhs), ldn, false};
+        for (int j = 0; j < nb_cols; ++j) h2d(c, bj.p + (size_t)ldm * j, rhs + (size_t)ldrhs * j, sizeof(double) * m);
+        if (xt_in) {
+            // x_true in the reference order, permuted into the operators' stored pixel order
+            double* tmp = po.trivial() ? nullptr : c->buf<double>((pre + "xt_ref").c_str(), n > 0 ? n : 1);
+            for (int j = 0; j < nxt_cols; ++j) {
+                double* dst = xtj.p + (size_t)ldn * j;
+                h2d(c, po.trivial() ? dst : tmp, xt_in + (size_t)ldxt * j, sizeof(double) * n);
+                if (!po.trivial()) pix_permute<double>(c, po, tmp, dst, 0);
+            }
+        } else if (zero_xt) {
+            HGM_HIP(hipMemsetAsync(xtj.p, 0, sizeof(double) * ldn, c->stream));
+        }
+    }
+
+    // the iterates into the columns of X_out, in the reference order (assigned: only the columns it marks)
+    void stage_out(hgm_ctx* c, double* X_out, int64_t ldx, const std::vector<char>* assigned = nullptr) const {
+        if (!X_out) return;
+        for (int j = 0; j < nrhs; ++j)
+            if (!assigned || (*assigned)[j]) stage_out_n<double>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
+    }
+};
+
+// the operator's entries once and the interleaved vectors once each way
+double spmm_bytes(const hgm_mat* M, int nv) { return 12.0 * M->nnz + 8.0 * spmm_width(nv) * (M->rows + M->cols); }
+
+// spmm as a KC_SPMM bracket of its own
+void spmm_timed(hgm_ctx* c, const hgm_mat* M, int nv, const double* in, double* out) {
+    hipEvent_t tev = nullptr;
+    timing_begin(c, KC_SPMM, &tev);
+    spmm(c, M, nv, in, out);
+    timing_end(c, KC_SPMM, tev, spmm_bytes(M, nv));
+}
+
 struct Lockstep {
     const double* rhs = nullptr;         // column j's right-hand side: rhs + ldrhs * j (host)
     int64_t ldrhs = 0;                   // 0: one b shared by every column
-    const hgm_mat* E = nullptr;          // perturbed B pass (nullptr: spmm(B))
-    const hgm_gauss* G = nullptr;        // ... or the matrix-free Gaussian for E (gauss.hip): spmm(B), then + c_j G
-    const double* coefs = nullptr;       // ... column j's coefficient
+    Perturbation P;                      // the B pass: spmm(B) (none), the perturbed product (P.E), or spmm(B)
+                                         // then + c_j G (P.G, gauss.hip); c_j = P.coefs[j]
     bool arnoldi = false;
     double btol = 0.0;                   // arnoldi: the break threshold
     double* beta_out = nullptr;          // arnoldi: ||r0|| per column
@@ -1773,18 +1851,17 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
                   int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, int* niters,
                   int* col_status) {
     const int64_t m = A->rows, n = A->cols;
-    const PixOrder po = n_order(c, A, B);
-    const bool pert = L.E != nullptr;
+    const bool pert = L.P.E != nullptr;
     // E on B's pattern: one compare pass over the index streams per solve
-    const bool pert_shared = pert && c->num.pert_shared && same_pattern(c, B, L.E);
+    const bool pert_shared = pert && c->num.pert_shared && same_pattern(c, B, L.P.E);
     const bool nspace = side == HGM_SIDE_BA;
     const int64_t dim = nspace ? n : m;
     const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
     const size_t hs = (size_t)(maxit + 1) * maxit;           // one column's Hessenberg
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (err_hist) std::fill(err_hist, err_hist + (size_t)maxit * nrhs, nan);
-    if (res_hist) std::fill(res_hist, res_hist + (size_t)maxit * nrhs, nan);
-    for (int j = 0; j < nrhs; ++j) niters[j] = 0;
+    // (the monitor reads x_true's column also without an x_true, so that one is zeroed: errors stay NaN)
+    const ColBatch cb(c, "bt_", A, n_order(c, A, B), nrhs, L.rhs, L.ldrhs, xt_in, ldxt, true, maxit,
+                      {err_hist, res_hist}, niters);
+    const ColBatch::Cols &bj = cb.bj, &xtj = cb.xtj, &xj = cb.xj;
     if (col_status) std::fill(col_status, col_status + nrhs, (int)HGM_OK);
 
     // ---- device storage: every per-column array is one slab with a constant column stride ----
@@ -1798,11 +1875,6 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
     auto kslot = [&](int k) { return L.arnoldi ? 0 : k; };
     double* Wall = c->buf<double>("bt_W", (size_t)ldm * kept * nrhs);
     double* Vall = nspace || L.arnoldi ? nullptr : c->buf<double>("bt_V", (size_t)ldn * kept * nrhs);
-    const int nb_cols = L.ldrhs == 0 ? 1 : nrhs;
-    double* ball = c->buf<double>("bt_b", (size_t)ldm * nb_cols);
-    const int nxt_cols = xt_in ? (ldxt == 0 ? 1 : nrhs) : 1;
-    double* xtall = c->buf<double>("bt_xt", (size_t)ldn * nxt_cols);
-    double* xall = c->buf<double>("bt_x", (size_t)ldn * nrhs);
     double* Hd = c->buf<double>("bt_H", hs * nrhs);
     double* Yd = c->buf<double>("bt_y", (size_t)maxit * nrhs);
     double* mon = c->buf<double>("bt_mon", (size_t)2 * nrhs);          // [res^2, err^2] per column
@@ -1817,22 +1889,6 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
     auto Wj = [&](int j) { return Wall + (size_t)ldm * kept * j; };
     auto Vj = [&](int j) -> const double* { return nspace ? Qj(j) : Vall + (size_t)ldn * kept * j; };
     const int64_t ldv = nspace ? ldq : ldn;
-    auto bj = [&](int j) { return ball + (size_t)ldm * (nb_cols == 1 ? 0 : j); };
-    auto xtj = [&](int j) -> const double* { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
-    auto xj = [&](int j) { return xall + (size_t)ldn * j; };
-
-    for (int j = 0; j < nb_cols; ++j) h2d(c, bj(j), L.rhs + (size_t)L.ldrhs * j, sizeof(double) * m);
-    if (xt_in) {
-        // x_true in the reference order, permuted into the operators' stored pixel order
-        double* tmp = po.trivial() ? nullptr : c->buf<double>("bt_xt_ref", n > 0 ? n : 1);
-        for (int j = 0; j < nxt_cols; ++j) {
-            double* dst = xtall + (size_t)ldn * j;
-            h2d(c, po.trivial() ? dst : tmp, xt_in + (size_t)ldxt * j, sizeof(double) * n);
-            if (!po.trivial()) pix_permute<double>(c, po, tmp, dst, 0);
-        }
-    } else {
-        HGM_HIP(hipMemsetAsync(xtall, 0, sizeof(double) * ldn, c->stream));   // the monitor's operand; errors stay NaN
-    }
 
     // per-column scratch of the orthogonalisation: the one-reduction MGS keeps its Gram triangle in a
     // workspace buffer from step to step, so every column gets workspace names of its own
@@ -1856,20 +1912,20 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
             ts.p[r] = const_cast<double*>(src(j));
             tm.p[r] = mid(j);
             td.p[r] = dst(j);
-            if (pert || L.G) cf[r] = L.coefs[j];
+            if (pert || L.P.G) cf[r] = L.P.coefs[j];
         }
         double bytes = 0.0;
         // one pass of the pair: spmm(A), and for B either spmm(B) or the perturbed product
         auto product = [&](const hgm_mat* M, const double* in, double* out) {
-            const double vec_bytes = 8.0 * spmm_width(nv) * (M->rows + M->cols);
             if (M == B && pert) {
-                spmm_pert(c, B, L.E, pert_shared, nv, cf, in, out);
-                bytes += (pert_shared ? 20.0 * B->nnz : 12.0 * ((double)B->nnz + L.E->nnz)) + vec_bytes;
+                spmm_pert(c, B, L.P.E, pert_shared, nv, cf, in, out);
+                bytes += (pert_shared ? 20.0 * B->nnz : 12.0 * ((double)B->nnz + L.P.E->nnz)) +
+                         8.0 * spmm_width(nv) * (M->rows + M->cols);
             } else {
-                spmm(c, M, nv, in, out);
-                bytes += 12.0 * M->nnz + vec_bytes;
+                spmm(c, M, nv, in, out);   // (inside this pass's one KC_SPMM bracket, so not spmm_timed)
+                bytes += spmm_bytes(M, nv);
                 // out = (B in) + (c_j * (G in)), G in the reference row order whatever B's stored one is
-                if (M == B && L.G) gauss_mm(c, L.G, B->row_order, nv, cf, true, in, out);
+                if (M == B && L.P.G) gauss_mm(c, L.P.G, B->row_order, nv, cf, true, in, out);
             }
         };
         hipEvent_t tev = nullptr;
@@ -2023,9 +2079,7 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
         }
         act.swap(next);
     }
-    if (X_out)
-        for (int j = 0; j < nrhs; ++j)
-            if (x_assigned[j]) stage_out_n<double>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
+    cb.stage_out(c, X_out, ldx, &x_assigned);
     if (H_out) std::memcpy(H_out, H.data(), sizeof(double) * H.size());
     if (L.beta_out) std::copy(beta.begin(), beta.end(), L.beta_out);
     if (unassigned)
@@ -2052,30 +2106,25 @@ void lockstep_lambdas(const double* lambdas, int ncols, int hybrid, const std::s
         HGM_REQUIRE(std::isfinite(lambdas[j]) && lambdas[j] >= 0.0, what + ": every lambda must be finite and >= 0");
 }
 
-// E and the coefficients of a mismatch sweep against its B0
-void mismatch_guard(const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs, int ncoef,
-                    const std::string& what) {
-    HGM_REQUIRE(E != nullptr, what + ": E is NULL");
-    HGM_REQUIRE(E->dtype == HGM_F64, what + ": fp64 operators only");
-    HGM_REQUIRE(A != B0 && E != A, what + ": A, B0 and E must be distinct operators");
-    HGM_REQUIRE(E->rows == B0->rows && E->cols == B0->cols, what + ": E must have B0's shape");
-    HGM_REQUIRE(E->row_order == B0->row_order && E->col_order == B0->col_order,
-                what + ": E must be stored in B0's row and column order");
-    HGM_REQUIRE(ncoef >= 1 && ncoef <= 64, what + ": 1 <= ncoef <= 64");
-    HGM_REQUIRE(coefs != nullptr, what + ": coefs is required");
-    for (int j = 0; j < ncoef; ++j) HGM_REQUIRE(std::isfinite(coefs[j]), what + ": every coefficient must be finite");
-}
-
-// G and the coefficients of a Gaussian mismatch sweep against its B0
-void mismatch_gauss_guard(const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G, const double* coefs, int ncoef,
-                          const std::string& what) {
-    HGM_REQUIRE(G != nullptr, what + ": G is NULL");
-    HGM_REQUIRE(A != B0, what + ": A and B0 must be distinct operators");
-    HGM_REQUIRE(G->rows == B0->rows && G->cols == B0->cols, what + ": G must have B0's shape");
-    HGM_REQUIRE(B0->col_order.trivial(), what + ": B0's columns must be in the reference order");
-    HGM_REQUIRE(ncoef >= 1 && ncoef <= 64, what + ": 1 <= ncoef <= 64");
-    HGM_REQUIRE(coefs != nullptr, what + ": coefs is required");
-    for (int j = 0; j < ncoef; ++j) HGM_REQUIRE(std::isfinite(coefs[j]), what + ": every coefficient must be finite");
+// the perturbation of a mismatch sweep (E or the Gaussian G, and the coefficients) against its B0
+void mismatch_guard(const hgm_mat* A, const hgm_mat* B0, const Perturbation& P, const std::string& what) {
+    if (P.G) {
+        HGM_REQUIRE(A != B0, what + ": A and B0 must be distinct operators");
+        HGM_REQUIRE(P.G->rows == B0->rows && P.G->cols == B0->cols, what + ": G must have B0's shape");
+        HGM_REQUIRE(B0->col_order.trivial(), what + ": B0's columns must be in the reference order");
+    } else {
+        const hgm_mat* E = P.E;
+        HGM_REQUIRE(E != nullptr, what + ": E is NULL");
+        HGM_REQUIRE(E->dtype == HGM_F64, what + ": fp64 operators only");
+        HGM_REQUIRE(A != B0 && E != A, what + ": A, B0 and E must be distinct operators");
+        HGM_REQUIRE(E->rows == B0->rows && E->cols == B0->cols, what + ": E must have B0's shape");
+        HGM_REQUIRE(E->row_order == B0->row_order && E->col_order == B0->col_order,
+                    what + ": E must be stored in B0's row and column order");
+    }
+    HGM_REQUIRE(P.ncoef >= 1 && P.ncoef <= 64, what + ": 1 <= ncoef <= 64");
+    HGM_REQUIRE(P.coefs != nullptr, what + ": coefs is required");
+    for (int j = 0; j < P.ncoef; ++j)
+        HGM_REQUIRE(std::isfinite(P.coefs[j]), what + ": every coefficient must be finite");
 }
 }  // namespace
 
@@ -2085,13 +2134,7 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                        double* res_hist, int* niters, int* col_status) {
     const std::string what = "batched solve";
     lockstep_guard(c, o, A, B, what);
-    HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, "batched solve: 1 <= nrhs <= 64");
-    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
-    HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
-    const int64_t m = A->rows, n = A->cols;
-    HGM_REQUIRE(ldb >= m, "batched solve: ldb >= rows(A)");
-    HGM_REQUIRE(X_out == nullptr || ldx >= n, "batched solve: ldx >= cols(A)");
-    HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, "batched solve: ldxt is 0 (one shared x_true) or >= cols(A)");
+    ColBatch::require(what, A, Bm, ldb, false, nrhs, xt_in, ldxt, maxit, X_out, ldx, niters);
     lockstep_lambdas(lambdas, nrhs, hybrid, what);
     Lockstep L;
     L.rhs = Bm;
@@ -2102,88 +2145,44 @@ int gmres_bounds_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
 
 // plot_error_vs_mismatch_norm.m:23-61 / run_2D_phantom.m:79-102: column j is the *_bounds solve of the
 // one b with the back-projector B0 + coefs[j] * E.  No such operator is formed: B0 and E are read once
-// per group of up to 8 running levels (spmm.hip k_spmm_pert).
-int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E,
-                          const double* coefs, int ncoef, const double* b, const double* xt_in, double tol, int maxit,
-                          const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx, double* err_hist,
-                          double* res_hist, int* niters, int* col_status) {
-    const std::string what = "mismatch sweep";
+// per group of up to 8 running levels (spmm.hip k_spmm_pert); with the matrix-free dense Gaussian G for E
+// (plot_error_vs_mismatch_norm.m:16-17: E = randn(size(A'))) nothing of G is stored, the B pass regenerates
+// it (gauss.hip).
+int gmres_bounds_mismatch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const Perturbation& P,
+                          const double* b, const double* xt_in, double tol, int maxit, const double* lambdas, int side,
+                          int hybrid, double* X_out, int64_t ldx, double* err_hist, double* res_hist, int* niters,
+                          int* col_status) {
+    const std::string what = P.G ? "Gaussian mismatch sweep" : "mismatch sweep";
     lockstep_guard(c, o, A, B0, what);
-    mismatch_guard(A, B0, E, coefs, ncoef, what);
+    mismatch_guard(A, B0, P, what);
     HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
     HGM_REQUIRE(b != nullptr && niters != nullptr, "b and niters are required");
     HGM_REQUIRE(X_out == nullptr || ldx >= A->cols, what + ": ldx >= cols(A)");
-    lockstep_lambdas(lambdas, ncoef, hybrid, what);
+    lockstep_lambdas(lambdas, P.ncoef, hybrid, what);
     Lockstep L;
     L.rhs = b;
-    L.E = E;
-    L.coefs = coefs;
-    return lockstep_core(c, L, o ? o->orth : HGM_MGS, o ? o->H_out : nullptr, A, B0, ncoef, xt_in, 0, tol, maxit,
+    L.P = P;
+    return lockstep_core(c, L, o ? o->orth : HGM_MGS, o ? o->H_out : nullptr, A, B0, P.ncoef, xt_in, 0, tol, maxit,
                          lambdas, side, hybrid, X_out, ldx, err_hist, res_hist, niters, col_status);
 }
 
 // gcv_function.m:3-33 for every level of a mismatch sweep in lockstep (the two GCV Arnoldis of
 // plot_error_vs_mismatch_norm.m:46-50): H holds ncoef consecutive (k+1) x k blocks.
-int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_mat* E, const double* coefs,
-                     int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
-                     double* beta_out, int* kdone) {
-    const std::string what = "mismatch Arnoldi";
+int arnoldi_mismatch(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const Perturbation& P, const double* b, int kg,
+                     int side, double btol, int orth, double* H_out, double* beta_out, int* kdone) {
+    const std::string what = P.G ? "Gaussian mismatch Arnoldi" : "mismatch Arnoldi";
     lockstep_guard(c, nullptr, A, B0, what);
-    mismatch_guard(A, B0, E, coefs, ncoef, what);
+    mismatch_guard(A, B0, P, what);
     HGM_REQUIRE(kg >= 1, "k must be >= 1");
     HGM_REQUIRE(b != nullptr, "b is required");
-    std::vector<int> done(ncoef, 0);
+    std::vector<int> done(P.ncoef, 0);
     Lockstep L;
     L.rhs = b;
-    L.E = E;
-    L.coefs = coefs;
+    L.P = P;
     L.arnoldi = true;
     L.btol = btol;
     L.beta_out = beta_out;
-    const int st = lockstep_core(c, L, orth, H_out, A, B0, ncoef, nullptr, 0, 0.0, kg, nullptr, side, 0, nullptr, 0,
-                                 nullptr, nullptr, done.data(), nullptr);
-    if (kdone) std::copy(done.begin(), done.end(), kdone);
-    return st;
-}
-
-// The two sweeps above with the matrix-free dense Gaussian G for E (plot_error_vs_mismatch_norm.m:16-17:
-// E = randn(size(A'))): nothing of G is stored, the B pass regenerates it (gauss.hip).
-int gmres_bounds_mismatch_gauss(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G,
-                                const double* coefs, int ncoef, const double* b, const double* xt_in, double tol,
-                                int maxit, const double* lambdas, int side, int hybrid, double* X_out, int64_t ldx,
-                                double* err_hist, double* res_hist, int* niters, int* col_status) {
-    const std::string what = "Gaussian mismatch sweep";
-    lockstep_guard(c, o, A, B0, what);
-    mismatch_gauss_guard(A, B0, G, coefs, ncoef, what);
-    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
-    HGM_REQUIRE(b != nullptr && niters != nullptr, "b and niters are required");
-    HGM_REQUIRE(X_out == nullptr || ldx >= A->cols, what + ": ldx >= cols(A)");
-    lockstep_lambdas(lambdas, ncoef, hybrid, what);
-    Lockstep L;
-    L.rhs = b;
-    L.G = G;
-    L.coefs = coefs;
-    return lockstep_core(c, L, o ? o->orth : HGM_MGS, o ? o->H_out : nullptr, A, B0, ncoef, xt_in, 0, tol, maxit,
-                         lambdas, side, hybrid, X_out, ldx, err_hist, res_hist, niters, col_status);
-}
-
-int arnoldi_mismatch_gauss(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B0, const hgm_gauss* G, const double* coefs,
-                           int ncoef, const double* b, int kg, int side, double btol, int orth, double* H_out,
-                           double* beta_out, int* kdone) {
-    const std::string what = "Gaussian mismatch Arnoldi";
-    lockstep_guard(c, nullptr, A, B0, what);
-    mismatch_gauss_guard(A, B0, G, coefs, ncoef, what);
-    HGM_REQUIRE(kg >= 1, "k must be >= 1");
-    HGM_REQUIRE(b != nullptr, "b is required");
-    std::vector<int> done(ncoef, 0);
-    Lockstep L;
-    L.rhs = b;
-    L.G = G;
-    L.coefs = coefs;
-    L.arnoldi = true;
-    L.btol = btol;
-    L.beta_out = beta_out;
-    const int st = lockstep_core(c, L, orth, H_out, A, B0, ncoef, nullptr, 0, 0.0, kg, nullptr, side, 0, nullptr, 0,
+    const int st = lockstep_core(c, L, orth, H_out, A, B0, P.ncoef, nullptr, 0, 0.0, kg, nullptr, side, 0, nullptr, 0,
                                  nullptr, nullptr, done.data(), nullptr);
     if (kdone) std::copy(done.begin(), done.end(), kdone);
     return st;
@@ -2219,23 +2218,16 @@ int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At,
     const std::string what = "Golub-Kahan batch";
     lockstep_guard(c, o, A, At, what);
     HGM_REQUIRE(kind == HGM_GK_LSQR || kind == HGM_GK_LSMR, what + ": kind is HGM_GK_LSQR or HGM_GK_LSMR");
-    HGM_REQUIRE(nrhs >= 1 && nrhs <= 64, what + ": 1 <= nrhs <= 64");
-    HGM_REQUIRE(maxit >= 1, "maxit must be >= 1");
-    HGM_REQUIRE(Bm != nullptr && niters != nullptr, "Bm and niters are required");
-    const int64_t m = A->rows, n = A->cols;
-    HGM_REQUIRE(ldb == 0 || ldb >= m, what + ": ldb is 0 (one shared b) or >= rows(A)");
-    HGM_REQUIRE(X_out == nullptr || ldx >= n, what + ": ldx >= cols(A)");
-    HGM_REQUIRE(xt_in == nullptr || ldxt == 0 || ldxt >= n, what + ": ldxt is 0 (one shared x_true) or >= cols(A)");
+    ColBatch::require(what, A, Bm, ldb, true, nrhs, xt_in, ldxt, maxit, X_out, ldx, niters);
     lockstep_lambdas(lambdas, nrhs, hybrid, what);
-    const PixOrder po = n_order(c, A, At);
+    const int64_t m = A->rows, n = A->cols;
     const bool lsmr = kind == HGM_GK_LSMR, hyb = hybrid != 0;
     const bool hlsqr = !lsmr && hyb, plsmr = lsmr && !hyb, hlsmr = lsmr && hyb;
-    const int64_t ldm = round_up(m > 0 ? m : 1, 64), ldn = round_up(n > 0 ? n : 1, 64);
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (err_hist) std::fill(err_hist, err_hist + (size_t)maxit * nrhs, nan);
-    if (res_hist) std::fill(res_hist, res_hist + (size_t)maxit * nrhs, nan);
-    if (ar_hist) std::fill(ar_hist, ar_hist + (size_t)maxit * nrhs, nan);
-    for (int j = 0; j < nrhs; ++j) niters[j] = 0;
+    const int64_t ldn = round_up(n > 0 ? n : 1, 64);
+    const ColBatch cb(c, "gk_", A, n_order(c, A, At), nrhs, Bm, ldb, xt_in, ldxt, false, maxit,
+                      {err_hist, res_hist, ar_hist}, niters);
+    const ColBatch::Cols &bj = cb.bj, &xtj = cb.xtj, &xj = cb.xj;
+    double* const xtall = xtj.p;
 
     // ---- device storage ----
     const size_t G0 = (size_t)(nrhs + SPMM_MAXV - 1) / SPMM_MAXV;
@@ -2258,11 +2250,6 @@ int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At,
     GkVec tmp_m = vec("gk_tmp_m", m), tmp_n = vec("gk_tmp_n", n);   // re-gather targets
     double* Tm = c->buf<double>("gk_tm", (size_t)(m > 0 ? m : 1) * SPMM_MAXV);   // one group's product
     double* Tn = c->buf<double>("gk_tn", (size_t)(n > 0 ? n : 1) * SPMM_MAXV);
-    const int nb_cols = ldb == 0 ? 1 : nrhs;
-    const int nxt_cols = xt_cols ? nrhs : 1;
-    double* ball = c->buf<double>("gk_ball", (size_t)ldm * nb_cols);
-    double* xtall = c->buf<double>("gk_xtall", (size_t)ldn * nxt_cols);
-    double* xall = c->buf<double>("gk_xall", (size_t)ldn * nrhs);
     double* dump = c->buf<double>("gk_dump", (size_t)ldn);   // where the slots of finished columns unpack to
     double* Vall = hlsmr ? c->buf<double>("gk_V", (size_t)ldn * maxit * nrhs) : nullptr;   // per-column bases V_j
     double* Yd = hlsmr ? c->buf<double>("gk_y", (size_t)maxit * nrhs) : nullptr;
@@ -2275,20 +2262,8 @@ int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At,
         rd.add(hsum.data(), dsum, sizeof(double) * (size_t)nq * G0 * SPMM_MAXV);
         rd.go();
     };
-    auto bj = [&](int j) { return ball + (size_t)ldm * (nb_cols == 1 ? 0 : j); };
-    auto xtj = [&](int j) { return xtall + (size_t)ldn * (nxt_cols == 1 ? 0 : j); };
-    auto xj = [&](int j) { return xall + (size_t)ldn * j; };
     auto Vj = [&](int j) { return Vall + (size_t)ldn * maxit * j; };
 
-    for (int j = 0; j < nb_cols; ++j) h2d(c, bj(j), Bm + (size_t)ldb * j, sizeof(double) * m);
-    if (xt_in) {
-        // x_true in the reference order, permuted into the operators' stored pixel order
-        double* tmp = po.trivial() ? nullptr : c->buf<double>("gk_xt_ref", n > 0 ? n : 1);
-        for (int j = 0; j < nxt_cols; ++j) {
-            h2d(c, po.trivial() ? xtj(j) : tmp, xt_in + (size_t)ldxt * j, sizeof(double) * n);
-            if (!po.trivial()) pix_permute<double>(c, po, tmp, xtj(j), 0);
-        }
-    }
     const int errmode = !xt_in ? MVS_NONE : xt_cols ? MVS_DIFF : MVS_DIFF_SHARED;
 
     // ---- the running columns, in groups of at most 8: slot -> column, -1 once the column has left ----
@@ -2305,12 +2280,7 @@ int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At,
         for (size_t r = 0; r < (size_t)SPMM_MAXV; ++r) k.c[r] = r < g.size() && g[r] >= 0 ? (double)f(g[r]) : dead;
         return k;
     };
-    auto product = [&](const hgm_mat* M, int nv, const double* in, double* out) {
-        hipEvent_t tev = nullptr;
-        timing_begin(c, KC_SPMM, &tev);
-        spmm(c, M, nv, in, out);
-        timing_end(c, KC_SPMM, tev, 12.0 * M->nnz + 8.0 * spmm_width(nv) * (M->rows + M->cols));
-    };
+    auto product = [&](const hgm_mat* M, int nv, const double* in, double* out) { spmm_timed(c, M, nv, in, out); };
     // a launch (or a few) of the interleaved vector kernels over nvecs multi-vectors of length len
     auto vk = [&](int64_t len, int nv, int nvecs, auto&& fn) {
         hipEvent_t tev = nullptr;
@@ -2642,8 +2612,7 @@ int gk_batch(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At,
         }
         if (left && running > 0) regather();
     }
-    if (X_out)
-        for (int j = 0; j < nrhs; ++j) stage_out_n<double>(c, X_out + (size_t)ldx * j, xj(j), n, false, po);
+    cb.stage_out(c, X_out, ldx);
     return HGM_OK;
 }
 

@@ -447,6 +447,55 @@ class SparseOperator:
             pass
 
 
+def _ld_view(M):
+    """(flat array to upload, leading dimension) of a 2-D array: a column-major view with a leading
+    dimension larger than its row count (``buf[:rows, :]`` of an ``ld x k`` Fortran array) is passed with
+    that leading dimension and its padding rows (except past the last column); anything else is copied
+    to a tight Fortran array."""
+    rows, k = M.shape
+    es = M.itemsize
+    if not (M.strides[0] == es and (k == 1 or (M.strides[1] % es == 0 and M.strides[1] >= rows * es))):
+        M = np.asfortranarray(M)
+    ld = rows if k == 1 else M.strides[1] // es
+    cnt = ld * (k - 1) + rows
+    flat = np.lib.stride_tricks.as_strided(M, shape=(cnt,), strides=(es,)) if ld != rows else M.reshape(-1, order="F")
+    return np.ascontiguousarray(flat), ld
+
+
+class _DevArrays:
+    """Device arrays of ``es``-byte elements for the device-pointer hooks (freed on exit)."""
+
+    def __init__(self, ctx, es=8):
+        self.ctx, self.lib, self.es, self.ptrs = ctx, L.load(), es, []
+
+    def alloc(self, count):
+        p = C.c_void_p()
+        _check(self.lib.hgm_dev_alloc(self.ctx.handle, self.es * max(1, int(count)), C.byref(p)), self.ctx)
+        self.ptrs.append(p)
+        return p
+
+    def upload(self, flat):
+        p = self.alloc(flat.size)
+        _check(self.lib.hgm_memcpy_h2d(self.ctx.handle, p, flat.ctypes.data_as(C.c_void_p), self.es * flat.size),
+               self.ctx)
+        return p
+
+    def download(self, p, out):
+        """Fill the host array ``out`` (contiguous in memory) from the device array ``p``."""
+        _check(self.lib.hgm_memcpy_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), p, self.es * out.size),
+               self.ctx)
+        return out
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.ptrs:
+            if p.value:
+                self.lib.hgm_dev_free(self.ctx.handle, p)
+        return False
+
+
 def spmv_ab(A: "SparseOperator", B: "SparseOperator", q):
     """(B*q, A*(B*q)) through ``hgm_spmv_ab`` (host arrays in, host arrays out): the m-space
     operator of the AB solvers, one pass over B when B is A' value for value (fused.hip)."""
@@ -458,27 +507,14 @@ def spmv_ab(A: "SparseOperator", B: "SparseOperator", q):
     q = np.ascontiguousarray(np.asarray(q, dtype=dt).reshape(-1))
     if q.shape[0] != m:
         raise ValueError(f"q has length {q.shape[0]}, expected {m}")
-    ptr = [C.c_void_p() for _ in range(3)]
-    try:
-        for p_, k in zip(ptr, (m, n, m)):
-            _check(lib.hgm_dev_alloc(ctx.handle, es * max(1, k), C.byref(p_)), ctx)
-        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], q.ctypes.data_as(C.c_void_p), es * m), ctx)
-        _check(lib.hgm_spmv_ab(ctx.handle, A._h, B._h, ptr[0], ptr[1], ptr[2]), ctx)
-        bq, abq = np.empty(n, dtype=dt), np.empty(m, dtype=dt)
-        _check(lib.hgm_memcpy_d2h(ctx.handle, bq.ctypes.data_as(C.c_void_p), ptr[1], es * n), ctx)
-        _check(lib.hgm_memcpy_d2h(ctx.handle, abq.ctypes.data_as(C.c_void_p), ptr[2], es * m), ctx)
-    finally:
-        for p_ in ptr:
-            if p_.value:
-                lib.hgm_dev_free(ctx.handle, p_)
+    with _DevArrays(ctx, es) as dev:
+        qd, bqd, abqd = dev.upload(q), dev.alloc(n), dev.alloc(m)
+        _check(lib.hgm_spmv_ab(ctx.handle, A._h, B._h, qd, bqd, abqd), ctx)
+        bq, abq = dev.download(bqd, np.empty(n, dtype=dt)), dev.download(abqd, np.empty(m, dtype=dt))
     return bq.astype(np.float64), abq.astype(np.float64)
 
 
-def spmm(A: "SparseOperator", X):
-    """``A @ X`` for an ``n x nvec`` host array ``X`` (``1 <= nvec <= 8``) through ``hgm_spmm``: the
-    operator's entries are read once for all columns (spmm.hip).  fp64 operators.  A column's bits do not
-    depend on ``nvec``, on its position, or on the other columns."""
-    m, n = A.shape
+def _mm_X(X, n, what):
     X = np.asarray(X, dtype=np.float64)
     if X.ndim == 1:
         X = X.reshape(-1, 1)
@@ -486,25 +522,29 @@ def spmm(A: "SparseOperator", X):
         raise ValueError(f"X has shape {X.shape}, expected ({n}, nvec)")
     nv = X.shape[1]
     if not 1 <= nv <= 8:
-        raise ValueError(f"spmm takes 1 to 8 vectors, not {nv}")
+        raise ValueError(f"{what} takes 1 to 8 vectors, not {nv}")
+    return X, nv
+
+
+def _mm_device(ctx, m, n, nv, X, call):
+    """Upload X (n x nv), run ``call(X_dev, Y_dev)``, download Y (m x nv)."""
+    with _DevArrays(ctx) as dev:
+        xd, yd = dev.upload(np.asfortranarray(X).reshape(-1, order="F")), dev.alloc(m * nv)
+        _check(call(xd, yd), ctx)
+        return dev.download(yd, np.empty((m, nv), order="F"))
+
+
+def spmm(A: "SparseOperator", X):
+    """``A @ X`` for an ``n x nvec`` host array ``X`` (``1 <= nvec <= 8``) through ``hgm_spmm``: the
+    operator's entries are read once for all columns (spmm.hip).  fp64 operators.  A column's bits do not
+    depend on ``nvec``, on its position, or on the other columns."""
+    m, n = A.shape
+    X, nv = _mm_X(X, n, "spmm")
     if A.dtype != L.HGM_F64:
         raise ValueError("spmm: fp64 operators only")
     ctx = A.ctx
     lib = L.load()
-    Xf = np.asfortranarray(X)
-    Y = np.empty((m, nv), order="F")
-    ptr = [C.c_void_p() for _ in range(2)]
-    try:
-        for p_, k in zip(ptr, (n * nv, m * nv)):
-            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, k), C.byref(p_)), ctx)
-        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
-        _check(lib.hgm_spmm(ctx.handle, A._h, nv, ptr[0], max(n, 1), ptr[1], max(m, 1)), ctx)
-        _check(lib.hgm_memcpy_d2h(ctx.handle, Y.ctypes.data_as(C.c_void_p), ptr[1], 8 * m * nv), ctx)
-    finally:
-        for p_ in ptr:
-            if p_.value:
-                lib.hgm_dev_free(ctx.handle, p_)
-    return Y
+    return _mm_device(ctx, m, n, nv, X, lambda xd, yd: lib.hgm_spmm(ctx.handle, A._h, nv, xd, max(n, 1), yd, max(m, 1)))
 
 
 class GaussianPerturbation:
@@ -613,37 +653,6 @@ def _scaled_coefs(cf, scale, what):
     return out
 
 
-def _mm_X(X, n, what):
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim == 1:
-        X = X.reshape(-1, 1)
-    if X.ndim != 2 or X.shape[0] != n:
-        raise ValueError(f"X has shape {X.shape}, expected ({n}, nvec)")
-    nv = X.shape[1]
-    if not 1 <= nv <= 8:
-        raise ValueError(f"{what} takes 1 to 8 vectors, not {nv}")
-    return X, nv
-
-
-def _mm_device(ctx, m, n, nv, X, call):
-    """Upload X (n x nv), run ``call(X_dev, Y_dev)``, download Y (m x nv)."""
-    lib = L.load()
-    Xf = np.asfortranarray(X)
-    Y = np.empty((m, nv), order="F")
-    ptr = [C.c_void_p() for _ in range(2)]
-    try:
-        for p_, k in zip(ptr, (n * nv, m * nv)):
-            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, k), C.byref(p_)), ctx)
-        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
-        _check(call(ptr[0], ptr[1]), ctx)
-        _check(lib.hgm_memcpy_d2h(ctx.handle, Y.ctypes.data_as(C.c_void_p), ptr[1], 8 * m * nv), ctx)
-    finally:
-        for p_ in ptr:
-            if p_.value:
-                lib.hgm_dev_free(ctx.handle, p_)
-    return Y
-
-
 def _spmm_pert_gauss(B0, G, coefs, X):
     if not isinstance(B0, SparseOperator):
         raise TypeError("B0 must be a SparseOperator (hgmres.as_operator)")
@@ -693,31 +702,12 @@ def spmm_pert(B0: "SparseOperator", E: "SparseOperator", coefs, X):
         return _spmm_pert_gauss(B0, E, coefs, X)
     _pert_pair(B0, E)
     m, n = B0.shape
-    X = np.asarray(X, dtype=np.float64)
-    if X.ndim == 1:
-        X = X.reshape(-1, 1)
-    if X.ndim != 2 or X.shape[0] != n:
-        raise ValueError(f"X has shape {X.shape}, expected ({n}, nvec)")
-    nv = X.shape[1]
-    if not 1 <= nv <= 8:
-        raise ValueError(f"spmm_pert takes 1 to 8 vectors, not {nv}")
+    X, nv = _mm_X(X, n, "spmm_pert")
     cf = _coefs(coefs, nv, nv, f"spmm_pert of {nv} vectors")
     ctx = B0.ctx
     lib = L.load()
-    Xf = np.asfortranarray(X)
-    Y = np.empty((m, nv), order="F")
-    ptr = [C.c_void_p() for _ in range(2)]
-    try:
-        for p_, k in zip(ptr, (n * nv, m * nv)):
-            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, k), C.byref(p_)), ctx)
-        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
-        _check(lib.hgm_spmm_pert(ctx.handle, B0._h, E._h, nv, _dp(cf), ptr[0], max(n, 1), ptr[1], max(m, 1)), ctx)
-        _check(lib.hgm_memcpy_d2h(ctx.handle, Y.ctypes.data_as(C.c_void_p), ptr[1], 8 * m * nv), ctx)
-    finally:
-        for p_ in ptr:
-            if p_.value:
-                lib.hgm_dev_free(ctx.handle, p_)
-    return Y
+    return _mm_device(ctx, m, n, nv, X, lambda xd, yd: lib.hgm_spmm_pert(ctx.handle, B0._h, E._h, nv, _dp(cf), xd,
+                                                                          max(n, 1), yd, max(m, 1)))
 
 
 def fused_plan_info(A: "SparseOperator", B: "SparseOperator"):
@@ -949,6 +939,53 @@ def gmres_lambda_sweep(A, B, b, x_true, tol, maxit, lambdas, side, *, ctx=None, 
                        H.reshape(maxit, maxit + 1).T.copy() if return_H else None, ks.value)
 
 
+def _col_lambdas(lambdas, ncols, noun):
+    """``lambdas`` (or None) as a contiguous vector with one entry per ``noun`` (``ncols`` None: any length)."""
+    if lambdas is None:
+        return None
+    lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+    if ncols is not None and lam.size != ncols:
+        raise ValueError(f"lambdas has {lam.size} entries, expected one per {noun} ({ncols})")
+    return lam
+
+
+def _col_x_true(x_true, n, ncols):
+    """``(xt, ldxt)`` of a lockstep solve: none, one vector shared by every column (``ldxt`` 0) or ``n x ncols``."""
+    if x_true is None:
+        return None, 0
+    xt = np.asarray(x_true, dtype=np.float64)
+    if xt.ndim == 1 or (xt.ndim == 2 and xt.shape[1] == 1 and ncols != 1):
+        return _f64(xt, n, "x_true"), 0                         # one column shared by every right-hand side
+    if xt.shape != (n, ncols):
+        raise ValueError(f"x_true has shape {xt.shape}, expected ({n},) or ({n}, {ncols})")
+    return np.asfortranarray(xt), max(n, 1)
+
+
+def _batch_outputs(n, maxit, ncols, nhist):
+    """``(X, histories, niters)`` of a lockstep solve before the call: NaN, and no iterations."""
+    return (np.full((n, ncols), np.nan, order="F"), [np.full((maxit, ncols), np.nan, order="F") for _ in range(nhist)],
+            np.zeros(ncols, dtype=np.int32))
+
+
+def _H_blocks(H, ncols, k):
+    """``ncols`` consecutive column-major ``(k+1) x k`` blocks as an ``ncols x (k+1) x k`` array."""
+    return H.reshape(ncols, k, k + 1).transpose(0, 2, 1).copy()
+
+
+def _bounds_lockstep(ctx, n, maxit, ncols, orth, return_H, call):
+    """The outputs of a lockstep ``*_bounds`` solve, ``call(opts, X, ldx, err, res, niters, status)`` and the
+    :class:`BatchResult`; a column without an x (breakdown at k = 1) does not raise."""
+    X, (err, res), nit = _batch_outputs(n, maxit, ncols, 2)
+    st = np.zeros(ncols, dtype=np.int32)
+    H = np.zeros((maxit + 1) * maxit * ncols) if return_H else None
+    o = _opts(orth, H)
+    ip = C.POINTER(C.c_int)
+    rc = call(C.byref(o), _dp(X), max(n, 1), _dp(err), _dp(res), nit.ctypes.data_as(ip), st.ctypes.data_as(ip))
+    if rc != L.HGM_E_NOT_ASSIGNED:
+        _check(rc, ctx)
+    return BatchResult(X, err, res, nit.astype(int), st.astype(int), _H_blocks(H, ncols, maxit) if return_H else None)
+
+
 class BatchResult:
     """Outputs of :func:`gmres_bounds_batch`.  ``x``: ``n x nrhs`` (a column that broke down at k = 1 is
     NaN); ``error_norm``, ``residual_norm``: ``maxit x nrhs`` (row k-1 = iteration k; NaN past
@@ -979,39 +1016,16 @@ def gmres_bounds_batch(A, B, Bm, x_true, tol, maxit, side, *, lambdas=None, ctx=
     nrhs = Bm.shape[1]
     if nrhs > 64:
         raise ValueError(f"at most 64 right-hand sides per call, not {nrhs}")
-    lam = None
-    if lambdas is not None:
-        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
-        if lam.size != nrhs:
-            raise ValueError(f"lambdas has {lam.size} entries, expected one per right-hand side ({nrhs})")
-    xt, ldxt = None, 0
-    if x_true is not None:
-        xt = np.asarray(x_true, dtype=np.float64)
-        if xt.ndim == 1 or (xt.ndim == 2 and xt.shape[1] == 1 and nrhs != 1):
-            xt = _f64(xt, n, "x_true")                              # one column shared by every right-hand side
-        elif xt.shape != (n, nrhs):
-            raise ValueError(f"x_true has shape {xt.shape}, expected ({n},) or ({n}, {nrhs})")
-        else:
-            xt, ldxt = np.asfortranarray(xt), max(n, 1)
+    lam = _col_lambdas(lambdas, nrhs, "right-hand side")
+    xt, ldxt = _col_x_true(x_true, n, nrhs)
     if maxit < 1:
         raise ValueError("maxit must be >= 1")
     ctx, Ao, Bo = _ops(A, B, ctx)
     Bf = np.asfortranarray(Bm)
-    X = np.full((n, nrhs), np.nan, order="F")
-    err = np.full((maxit, nrhs), np.nan, order="F")
-    res = np.full((maxit, nrhs), np.nan, order="F")
-    nit = np.zeros(nrhs, dtype=np.int32)
-    st = np.zeros(nrhs, dtype=np.int32)
-    H = np.zeros((maxit + 1) * maxit * nrhs) if return_H else None
-    o = _opts(orth, H)
-    ip = C.POINTER(C.c_int)
-    rc = L.load().hgm_gmres_bounds_batch(ctx.handle, C.byref(o), Ao._h, Bo._h, _dp(Bf), max(m, 1), nrhs, _dp(xt), ldxt,
-                                         float(tol), maxit, _dp(lam), sd, 0 if lam is None else 1, _dp(X), max(n, 1),
-                                         _dp(err), _dp(res), nit.ctypes.data_as(ip), st.ctypes.data_as(ip))
-    if rc != L.HGM_E_NOT_ASSIGNED:
-        _check(rc, ctx)
-    return BatchResult(X, err, res, nit.astype(int), st.astype(int),
-                       H.reshape(nrhs, maxit, maxit + 1).transpose(0, 2, 1).copy() if return_H else None)
+    fn = L.load().hgm_gmres_bounds_batch
+    return _bounds_lockstep(ctx, n, maxit, nrhs, orth, return_H, lambda o, *out: fn(
+        ctx.handle, o, Ao._h, Bo._h, _dp(Bf), max(m, 1), nrhs, _dp(xt), ldxt, float(tol), maxit, _dp(lam), sd,
+        0 if lam is None else 1, *out))
 
 
 def _mismatch_args(A, B0, E, coefs, b, what):
@@ -1055,29 +1069,13 @@ def gmres_bounds_mismatch(A, B0, E, coefs, b, x_true, tol, maxit, side, *, lambd
     maxit = int(maxit)
     if maxit < 1:
         raise ValueError("maxit must be >= 1")
-    lam = None
-    if lambdas is not None:
-        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
-        if lam.size != nc:
-            raise ValueError(f"lambdas has {lam.size} entries, expected one per coefficient ({nc})")
+    lam = _col_lambdas(lambdas, nc, "coefficient")
     xt = _f64(x_true, n, "x_true") if x_true is not None else None
     ctx, Ao, Bo, Eo = _mismatch_ops(A, B0, E, ctx)
-    X = np.full((n, nc), np.nan, order="F")
-    err = np.full((maxit, nc), np.nan, order="F")
-    res = np.full((maxit, nc), np.nan, order="F")
-    nit = np.zeros(nc, dtype=np.int32)
-    st = np.zeros(nc, dtype=np.int32)
-    H = np.zeros((maxit + 1) * maxit * nc) if return_H else None
-    o = _opts(orth, H)
-    ip = C.POINTER(C.c_int)
     fn = L.load().hgm_gmres_bounds_mismatch_gauss if gauss else L.load().hgm_gmres_bounds_mismatch
-    rc = fn(ctx.handle, C.byref(o), Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), _dp(xt), float(tol), maxit, _dp(lam), sd,
-            0 if lam is None else 1, _dp(X), max(n, 1), _dp(err), _dp(res), nit.ctypes.data_as(ip),
-            st.ctypes.data_as(ip))
-    if rc != L.HGM_E_NOT_ASSIGNED:
-        _check(rc, ctx)
-    return BatchResult(X, err, res, nit.astype(int), st.astype(int),
-                       H.reshape(nc, maxit, maxit + 1).transpose(0, 2, 1).copy() if return_H else None)
+    return _bounds_lockstep(ctx, n, maxit, nc, orth, return_H, lambda o, *out: fn(
+        ctx.handle, o, Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), _dp(xt), float(tol), maxit, _dp(lam), sd,
+        0 if lam is None else 1, *out))
 
 
 def arnoldi_mismatch(A, B0, E, coefs, b, k, gcv_type="ba", *, ctx=None, breakdown_tol=1e-12, orth="mgs"):
@@ -1102,7 +1100,7 @@ def arnoldi_mismatch(A, B0, E, coefs, b, k, gcv_type="ba", *, ctx=None, breakdow
     fn = L.load().hgm_arnoldi_mismatch_gauss if gauss else L.load().hgm_arnoldi_mismatch
     _check(fn(ctx.handle, Ao._h, Bo._h, Eo._h, _dp(cf), nc, _dp(b), k, sd, float(breakdown_tol), o, _dp(H), _dp(beta),
               kd.ctypes.data_as(C.POINTER(C.c_int))), ctx)
-    return H.reshape(nc, k, k + 1).transpose(0, 2, 1).copy(), beta, kd.astype(int)
+    return _H_blocks(H, nc, k), beta, kd.astype(int)
 
 
 def proj_norms(V, Y, t=None, *, ctx=None, loop=False):
@@ -1122,35 +1120,17 @@ def proj_norms(V, Y, t=None, *, ctx=None, loop=False):
         raise ValueError("proj_norms: rows, k and L must be >= 1")
     ctx = ctx or default_context()
     lib = L.load()
-    es = V.itemsize
-    if not (V.strides[0] == es and (k == 1 or (V.strides[1] % es == 0 and V.strides[1] >= rows * es))):
-        V = np.asfortranarray(V)
-    ldv = rows if k == 1 else V.strides[1] // es
-    # the whole leading-dimension span is uploaded (padding rows included), except past the last column
-    nv = ldv * (k - 1) + rows
-    vflat = np.lib.stride_tricks.as_strided(V, shape=(nv,), strides=(es,)) if ldv != rows else V.reshape(-1, order="F")
-    vflat = np.ascontiguousarray(vflat)
+    vflat, ldv = _ld_view(V)
     tt = _f64(t, rows, "t") if t is not None else None
-    ptr = [C.c_void_p() for _ in range(3)]
     d, s = np.zeros(nl), np.zeros(nl)
-    try:
-        for p_, cnt in zip(ptr, (nv, k * nl, rows)):
-            _check(lib.hgm_dev_alloc(ctx.handle, 8 * max(1, cnt), C.byref(p_)), ctx)
-        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], vflat.ctypes.data_as(C.c_void_p), 8 * nv), ctx)
-        _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[1], Y.ctypes.data_as(C.c_void_p), 8 * k * nl), ctx)
-        if tt is not None:
-            _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[2], tt.ctypes.data_as(C.c_void_p), 8 * rows), ctx)
+    with _DevArrays(ctx) as dev:
+        vd, yd = dev.upload(vflat), dev.upload(Y.reshape(-1, order="F"))
+        td = dev.upload(tt) if tt is not None else None
         if loop:
-            _check(lib.hgm_proj_norms_loop(ctx.handle, rows, k, ptr[0], ldv, ptr[1], k, nl,
-                                           ptr[2] if tt is not None else None, _dp(d)), ctx)
+            _check(lib.hgm_proj_norms_loop(ctx.handle, rows, k, vd, ldv, yd, k, nl, td, _dp(d)), ctx)
             s = None
         else:
-            _check(lib.hgm_proj_norms(ctx.handle, rows, k, ptr[0], ldv, ptr[1], k, nl,
-                                      ptr[2] if tt is not None else None, _dp(d), _dp(s)), ctx)
-    finally:
-        for p_ in ptr:
-            if p_.value:
-                lib.hgm_dev_free(ctx.handle, p_)
+            _check(lib.hgm_proj_norms(ctx.handle, rows, k, vd, ldv, yd, k, nl, td, _dp(d), _dp(s)), ctx)
     return d, s
 
 
@@ -1161,8 +1141,9 @@ def _gkb_ops(A, ctx, At=None, dtype=L.HGM_F64):
     return ctx, Ao, Ato
 
 
-def lsqr_solver(A, b, x_true, tol, maxit, *, ctx=None, At=None):
-    """``[x, error_norm, residual_norm, niters] = lsqr_solver(A,b,x_true,tol,maxit)`` (lsqr_solver.m:1-54)."""
+def _gkb_solve(fn_name, A, b, x_true, tol, maxit, ctx, At, lambda_=None):
+    """The one body of lsqr_solver (``lambda_`` None: the ``_ex`` signature with options) and the two hybrid
+    solvers (lambda after maxit)."""
     ctx, Ao, Ato = _gkb_ops(A, ctx, At)
     m, n = Ao.shape
     maxit = int(maxit)
@@ -1170,10 +1151,16 @@ def lsqr_solver(A, b, x_true, tol, maxit, *, ctx=None, At=None):
     xt = _f64(x_true, n, "x_true")
     x, err, res, it = np.zeros(n), np.zeros(maxit), np.zeros(maxit), C.c_int(0)
     o = _opts()
-    _check(L.load().hgm_lsqr_solver_ex(ctx.handle, C.byref(o), Ao._h, Ato._h, _dp(b), _dp(xt), float(tol), maxit,
-                                       _dp(x), _dp(err), _dp(res), C.byref(it)), ctx)
+    head, lam = ((C.byref(o),), ()) if lambda_ is None else ((), (float(lambda_),))
+    _check(getattr(L.load(), fn_name)(ctx.handle, *head, Ao._h, Ato._h, _dp(b), _dp(xt), float(tol), maxit, *lam,
+                                      _dp(x), _dp(err), _dp(res), C.byref(it)), ctx)
     k = it.value
     return x, err[:k].copy(), res[:k].copy(), k
+
+
+def lsqr_solver(A, b, x_true, tol, maxit, *, ctx=None, At=None):
+    """``[x, error_norm, residual_norm, niters] = lsqr_solver(A,b,x_true,tol,maxit)`` (lsqr_solver.m:1-54)."""
+    return _gkb_solve("hgm_lsqr_solver_ex", A, b, x_true, tol, maxit, ctx, At)
 
 
 def lsmr_solver(A, b, x_true=None, tol=None, maxit=None, *, ctx=None, At=None, explicit_residual=False):
@@ -1197,30 +1184,12 @@ def lsmr_solver(A, b, x_true=None, tol=None, maxit=None, *, ctx=None, At=None, e
 
 def hybrid_lsqr_solver(A, b, x_true, tol, maxit, lambda_, *, ctx=None, At=None):
     """``hybrid_lsqr_solver.m:1-52`` (LSQR on ``[A; sqrt(lambda) I]``, augmentation implicit)."""
-    ctx, Ao, Ato = _gkb_ops(A, ctx, At)
-    m, n = Ao.shape
-    maxit = int(maxit)
-    b = _f64(b, m, "b")
-    xt = _f64(x_true, n, "x_true")
-    x, err, res, it = np.zeros(n), np.zeros(maxit), np.zeros(maxit), C.c_int(0)
-    _check(L.load().hgm_hybrid_lsqr_solver(ctx.handle, Ao._h, Ato._h, _dp(b), _dp(xt), float(tol), maxit,
-                                           float(lambda_), _dp(x), _dp(err), _dp(res), C.byref(it)), ctx)
-    k = it.value
-    return x, err[:k].copy(), res[:k].copy(), k
+    return _gkb_solve("hgm_hybrid_lsqr_solver", A, b, x_true, tol, maxit, ctx, At, lambda_)
 
 
 def hybrid_lsmr_solver(A, b, x_true, tol, maxit, lambda_, *, ctx=None, At=None):
     """``hybrid_lsmr_solver.m:1-57``."""
-    ctx, Ao, Ato = _gkb_ops(A, ctx, At)
-    m, n = Ao.shape
-    maxit = int(maxit)
-    b = _f64(b, m, "b")
-    xt = _f64(x_true, n, "x_true")
-    x, err, res, it = np.zeros(n), np.zeros(maxit), np.zeros(maxit), C.c_int(0)
-    _check(L.load().hgm_hybrid_lsmr_solver(ctx.handle, Ao._h, Ato._h, _dp(b), _dp(xt), float(tol), maxit,
-                                           float(lambda_), _dp(x), _dp(err), _dp(res), C.byref(it)), ctx)
-    k = it.value
-    return x, err[:k].copy(), res[:k].copy(), k
+    return _gkb_solve("hgm_hybrid_lsmr_solver", A, b, x_true, tol, maxit, ctx, At, lambda_)
 
 
 class GKBatchResult:
@@ -1250,9 +1219,7 @@ def gk_batch(A, Bm, x_true, tol, maxit, kind, *, lambdas=None, At=None, ctx=None
     kd, hybrid = GK_KINDS[str(kind).lower()]
     m, n = A.shape
     maxit = int(maxit)
-    lam = None
-    if lambdas is not None:
-        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+    lam = _col_lambdas(lambdas, None, "column")
     if hybrid and lam is None:
         raise ValueError(f"kind {kind!r} needs lambdas (one per column)")
     Bm = np.asarray(Bm, dtype=np.float64)
@@ -1269,28 +1236,17 @@ def gk_batch(A, Bm, x_true, tol, maxit, kind, *, lambdas=None, At=None, ctx=None
         nrhs = Bm.shape[1]
     if nrhs > 64:
         raise ValueError(f"at most 64 columns per call, not {nrhs}")
-    if lam is not None and lam.size != nrhs:
-        raise ValueError(f"lambdas has {lam.size} entries, expected one per column ({nrhs})")
+    lam = _col_lambdas(lam, nrhs, "column")
     if hybrid and not (np.all(np.isfinite(lam)) and np.all(lam >= 0)):
         raise ValueError("every lambda must be finite and >= 0")
-    xt, ldxt = None, 0
-    if x_true is not None:
-        xt = np.asarray(x_true, dtype=np.float64)
-        if xt.ndim == 1 or (xt.ndim == 2 and xt.shape[1] == 1 and nrhs != 1):
-            xt = _f64(xt, n, "x_true")                              # one column shared by every right-hand side
-        elif xt.shape != (n, nrhs):
-            raise ValueError(f"x_true has shape {xt.shape}, expected ({n},) or ({n}, {nrhs})")
-        else:
-            xt, ldxt = np.asfortranarray(xt), max(n, 1)
+    xt, ldxt = _col_x_true(x_true, n, nrhs)
     if maxit < 1:
         raise ValueError("maxit must be >= 1")
     if At is not None and tuple(At.shape) != (n, m):
         raise ValueError(f"At has shape {tuple(At.shape)}, expected ({n}, {m})")
     ctx, Ao, Ato = _gkb_ops(A, ctx, At)
     Bf = np.ascontiguousarray(Bm) if shared_b else np.asfortranarray(Bm)
-    X = np.full((n, nrhs), np.nan, order="F")
-    err, res, ar = (np.full((maxit, nrhs), np.nan, order="F") for _ in range(3))
-    nit = np.zeros(nrhs, dtype=np.int32)
+    X, (err, res, ar), nit = _batch_outputs(n, maxit, nrhs, 3)
     o = _opts()
     _check(L.load().hgm_gk_batch(ctx.handle, C.byref(o), Ao._h, Ato._h, _dp(Bf), 0 if shared_b else max(m, 1), nrhs,
                                  _dp(xt), ldxt, float(tol), maxit, _dp(lam), kd, hybrid, _dp(X), max(n, 1), _dp(err),
@@ -1317,26 +1273,13 @@ def mv_axpby_norms(a, X, b, Y, ctx=None):
     af = _coefs_any(a, nv, "a")
     bf = _coefs_any(b, nv, "b")
     ctx = ctx or default_context()
-    lib = L.load()
-    Xf, Yf = np.asfortranarray(X), np.asfortranarray(Y)
-    Out = np.empty((n, nv), order="F")
     ss = np.zeros(nv)
-    ptr = [C.c_void_p() for _ in range(3)]
     ld = max(n, 1)
-    try:
-        for p_ in ptr:
-            _check(lib.hgm_dev_alloc(ctx.handle, 8 * ld * nv, C.byref(p_)), ctx)
-        if n:
-            _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[0], Xf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
-            _check(lib.hgm_memcpy_h2d(ctx.handle, ptr[1], Yf.ctypes.data_as(C.c_void_p), 8 * n * nv), ctx)
-        _check(lib.hgm_mv_axpby_norms(ctx.handle, n, nv, _dp(af), ptr[0], ld, _dp(bf), ptr[1], ld, ptr[2], ld, _dp(ss)),
-               ctx)
-        if n:
-            _check(lib.hgm_memcpy_d2h(ctx.handle, Out.ctypes.data_as(C.c_void_p), ptr[2], 8 * n * nv), ctx)
-    finally:
-        for p_ in ptr:
-            if p_.value:
-                lib.hgm_dev_free(ctx.handle, p_)
+    with _DevArrays(ctx) as dev:
+        xd, yd = (dev.upload(np.asfortranarray(M).reshape(-1, order="F")) for M in (X, Y))
+        od = dev.alloc(ld * nv)
+        _check(dev.lib.hgm_mv_axpby_norms(ctx.handle, n, nv, _dp(af), xd, ld, _dp(bf), yd, ld, od, ld, _dp(ss)), ctx)
+        Out = dev.download(od, np.empty((n, nv), order="F"))
     return Out, ss
 
 
@@ -1455,48 +1398,6 @@ def ritz(Hp, h_next, G, nev):
 
 
 # ---- leading singular triplets and empirical filter factors (plot_filter_factors.m:30-40) ----
-def _ld_view(M):
-    """(flat array to upload, leading dimension) of a 2-D array: a column-major view with a leading
-    dimension larger than its row count (``buf[:rows, :]`` of an ``ld x k`` Fortran array) is passed with
-    that leading dimension and its padding rows (except past the last column); anything else is copied
-    to a tight Fortran array."""
-    rows, k = M.shape
-    es = M.itemsize
-    if not (M.strides[0] == es and (k == 1 or (M.strides[1] % es == 0 and M.strides[1] >= rows * es))):
-        M = np.asfortranarray(M)
-    ld = rows if k == 1 else M.strides[1] // es
-    cnt = ld * (k - 1) + rows
-    flat = np.lib.stride_tricks.as_strided(M, shape=(cnt,), strides=(es,)) if ld != rows else M.reshape(-1, order="F")
-    return np.ascontiguousarray(flat), ld
-
-
-class _DevArrays:
-    """Device copies of host arrays for the device-pointer hooks (freed on exit)."""
-
-    def __init__(self, ctx):
-        self.ctx, self.lib, self.ptrs = ctx, L.load(), []
-
-    def alloc(self, count):
-        p = C.c_void_p()
-        _check(self.lib.hgm_dev_alloc(self.ctx.handle, 8 * max(1, int(count)), C.byref(p)), self.ctx)
-        self.ptrs.append(p)
-        return p
-
-    def upload(self, flat):
-        p = self.alloc(flat.size)
-        _check(self.lib.hgm_memcpy_h2d(self.ctx.handle, p, flat.ctypes.data_as(C.c_void_p), 8 * flat.size), self.ctx)
-        return p
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.ptrs:
-            if p.value:
-                self.lib.hgm_dev_free(self.ctx.handle, p)
-        return False
-
-
 def basis_project(Q, X, *, loop=False, ctx=None):
     """``C = Q.T @ X`` (k x nx) from the device primitive ``hgm_basis_project``: one pass over the basis
     ``Q`` (rows x k, k <= 256) per group of up to 8 columns of ``X`` (rows x nx).  Column-major views with

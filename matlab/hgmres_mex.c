@@ -486,6 +486,97 @@ static void lambda_sweep(int nlhs, mxArray* plhs[], const mxArray* prhs[]) {
     if (nlhs > 4) plhs[4] = X;
 }
 
+/* ---- the lockstep commands: shared argument rules and outputs ---- */
+
+/* The lambdas argument prhs[idx] of a hybrid lockstep command: a dense vector with one finite entry >= 0 per `noun`
+ * (*ncols of them).  ldb != NULL: with one column of Bm, several lambdas (at most 64) are one b shared by every
+ * lambda; *ncols becomes their count and *ldb 0. */
+static const double* lambdas_arg(int nrhs, const mxArray* prhs[], int idx, const char* noun, int64_t* ncols,
+                                 int64_t* ldb) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "hgmres: the hybrid solvers need lambdas (one per %s)", noun);
+    if (nrhs <= idx) fail("hgmres:arg", msg);
+    need_double(prhs[idx], "lambdas");
+    const int64_t nl = (int64_t)mxGetNumberOfElements(prhs[idx]);
+    const int shared_b = ldb && *ncols == 1 && nl > 1 && nl <= 64;
+    snprintf(msg, sizeof msg, "hgmres: lambdas must be a dense vector with one entry per %s", noun);
+    if (mxIsSparse(prhs[idx]) || (nl != *ncols && !shared_b)) fail("hgmres:arg", msg);
+    if (shared_b) {
+        *ncols = nl;
+        *ldb = 0;
+    }
+    const double* lam = mxGetDoubles(prhs[idx]);
+    for (int64_t j = 0; j < nl; ++j)
+        if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
+    return lam;
+}
+
+/* x_true of a column batch: [] (NULL), size(A,2) x 1 shared by every column (*ldxt = 0), or one column each */
+static const double* x_true_cols(const mxArray* a, int64_t n, int64_t ncols, int64_t* ldxt) {
+    *ldxt = 0;
+    if (mxIsEmpty(a)) return NULL;
+    need_double(a, "x_true");
+    const int64_t xm = (int64_t)mxGetM(a), xn = (int64_t)mxGetN(a);
+    if (mxIsSparse(a) || xm != n || (xn != 1 && xn != ncols))
+        fail("hgmres:arg", "hgmres: x_true must be dense, size(A,2) x 1 or size(A,2) x nrhs, or []");
+    *ldxt = xn == 1 && ncols != 1 ? 0 : n;
+    return mxGetDoubles(a);
+}
+
+/* The 1 to 64 mismatch levels (*nc of them), each finite.  scale != NULL: every level times *scale (one rounding)
+ * must be finite, and unless the scale is 1 the products are returned in an mxCalloc'd copy (*owned, to mxFree). */
+static const double* coefs_arg(const mxArray* a, const double* scale, int64_t* nc, double** owned) {
+    need_double(a, "coefs");
+    *nc = (int64_t)mxGetNumberOfElements(a);
+    if (mxIsSparse(a) || *nc < 1 || *nc > 64)
+        fail("hgmres:arg", "hgmres: coefs must be a dense vector of 1 to 64 mismatch levels");
+    const double* cf = mxGetDoubles(a);
+    *owned = scale && *scale != 1.0 ? (double*)mxCalloc((size_t)*nc, sizeof(double)) : NULL;
+    for (int64_t j = 0; j < *nc; ++j) {
+        if (*owned) (*owned)[j] = cf[j] * *scale;
+        if (!isfinite(*owned ? (*owned)[j] : cf[j]))
+            fail("hgmres:arg", scale ? "hgmres: every coefficient times the scale must be finite"
+                                     : "hgmres: every coefficient must be finite");
+    }
+    return *owned ? *owned : cf;
+}
+
+/* the outputs of a lockstep command: X (n x nc, NaN until a column is assigned), nh histories (maxit x nc), the
+ * iteration counts and, with status, the per-column status */
+typedef struct {
+    mxArray *X, *h[3];
+    int *nit, *cst;
+    int nh;
+    int64_t nc;
+} batch_out;
+
+static batch_out batch_alloc(int64_t n, int maxit, int64_t nc, int nh, int status) {
+    batch_out o;
+    o.nh = nh;
+    o.nc = nc;
+    o.X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nc, mxREAL);
+    for (int i = 0; i < nh; ++i) o.h[i] = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
+    o.nit = (int*)mxCalloc((size_t)nc, sizeof(int));
+    o.cst = status ? (int*)mxCalloc((size_t)nc, sizeof(int)) : NULL;
+    for (int64_t i = 0; i < n * nc; ++i) mxGetDoubles(o.X)[i] = (double)NAN;
+    return o;
+}
+
+/* [X, histories..., niters [, status]] into plhs; the int buffers are freed */
+static void batch_return(batch_out* o, int nlhs, mxArray* plhs[]) {
+    int k = 0;
+    plhs[k++] = o->X;
+    for (int i = 0; i < o->nh; ++i)
+        if (nlhs > k) plhs[k++] = o->h[i];
+    int* counts[2] = {o->nit, o->cst};
+    for (int i = 0; i < 2 && counts[i]; ++i) {
+        mxArray* a = mxCreateDoubleMatrix((mwSize)o->nc, 1, mxREAL);
+        for (int64_t j = 0; j < o->nc; ++j) mxGetDoubles(a)[j] = (double)counts[i][j];
+        mxFree(counts[i]);
+        if (nlhs > k) plhs[k++] = a;
+    }
+}
+
 /* [X, error_hist, residual_hist, niters, status] = hgmres_mex('gmres_bounds_batch', side, hybrid, A, B, Bm, x_true,
  * tol, maxit [, lambdas]).  Side, hybrid, every size and the lambdas are checked before a device is touched. */
 static void bounds_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -497,194 +588,75 @@ static void bounds_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prh
     if ((int64_t)mxGetM(prhs[4]) != n || (int64_t)mxGetN(prhs[4]) != m)
         fail("hgmres:arg", "hgmres: B must be size(A')");
     need_double(prhs[5], "Bm");
-    const int64_t nb = (int64_t)mxGetN(prhs[5]);
+    int64_t nb = (int64_t)mxGetN(prhs[5]), ldxt;
     if (mxIsSparse(prhs[5]) || (int64_t)mxGetM(prhs[5]) != m || nb < 1 || nb > 64)
         fail("hgmres:arg", "hgmres: Bm must be a dense size(A,1) x nrhs matrix with 1 <= nrhs <= 64");
-    const double* xt = NULL;
-    int64_t ldxt = 0;
-    if (!mxIsEmpty(prhs[6])) {
-        need_double(prhs[6], "x_true");
-        const int64_t xm = (int64_t)mxGetM(prhs[6]), xn = (int64_t)mxGetN(prhs[6]);
-        if (mxIsSparse(prhs[6]) || xm != n || (xn != 1 && xn != nb))
-            fail("hgmres:arg", "hgmres: x_true must be dense, size(A,2) x 1 or size(A,2) x nrhs, or []");
-        xt = mxGetDoubles(prhs[6]);
-        ldxt = xn == 1 && nb != 1 ? 0 : n;
-    }
+    const double* xt = x_true_cols(prhs[6], n, nb, &ldxt);
     const double tol = scalar(prhs[7], "tol");
     const int maxit = maxit_of(prhs[8]);
-    const double* lam = NULL;
-    if (hybrid) {
-        if (nrhs < 10) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per right-hand side)");
-        need_double(prhs[9], "lambdas");
-        if (mxIsSparse(prhs[9]) || (int64_t)mxGetNumberOfElements(prhs[9]) != nb)
-            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per right-hand side");
-        lam = mxGetDoubles(prhs[9]);
-        for (int64_t j = 0; j < nb; ++j)
-            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
-    }
+    const double* lam = hybrid ? lambdas_arg(nrhs, prhs, 9, "right-hand side", &nb, NULL) : NULL;
     hgm_mat* A = op(prhs[3], "A");
     check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
     hgm_mat* B = op(prhs[4], "B");
-    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nb, mxREAL);
-    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
-    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
-    int* nit = (int*)mxCalloc((size_t)nb, sizeof(int));
-    int* cst = (int*)mxCalloc((size_t)nb, sizeof(int));
-    for (int64_t i = 0; i < n * nb; ++i) mxGetDoubles(X)[i] = (double)NAN;
+    batch_out o = batch_alloc(n, maxit, nb, 2, 1);
     const int st = hgm_gmres_bounds_batch(ctx(), NULL, A, B, mxGetDoubles(prhs[5]), m > 0 ? m : 1, (int)nb, xt, ldxt, tol,
-                                          maxit, lam, side, hybrid, mxGetDoubles(X), n > 0 ? n : 1, mxGetDoubles(e),
-                                          mxGetDoubles(r), nit, cst);
+                                          maxit, lam, side, hybrid, mxGetDoubles(o.X), n > 0 ? n : 1,
+                                          mxGetDoubles(o.h[0]), mxGetDoubles(o.h[1]), o.nit, o.cst);
     if (st != HGM_E_NOT_ASSIGNED) check(st);             /* unassigned columns are reported in status */
-    mxArray* ni = mxCreateDoubleMatrix((mwSize)nb, 1, mxREAL);
-    mxArray* cs = mxCreateDoubleMatrix((mwSize)nb, 1, mxREAL);
-    for (int64_t j = 0; j < nb; ++j) {
-        mxGetDoubles(ni)[j] = (double)nit[j];
-        mxGetDoubles(cs)[j] = (double)cst[j];
-    }
-    mxFree(nit);
-    mxFree(cst);
-    plhs[0] = X;
-    if (nlhs > 1) plhs[1] = e;
-    if (nlhs > 2) plhs[2] = r;
-    if (nlhs > 3) plhs[3] = ni;
-    if (nlhs > 4) plhs[4] = cs;
+    batch_return(&o, nlhs, plhs);
 }
 
 /* [X, error_hist, residual_hist, niters, status] = hgmres_mex('gmres_bounds_mismatch', side, hybrid, A, B0, E, coefs,
- * b, x_true, tol, maxit [, lambdas]).  Side, hybrid, every size, the coefficients and the lambdas are checked
- * before a device is touched. */
-static void bounds_mismatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+ * b, x_true, tol, maxit [, lambdas]), and with gauss 'gmres_bounds_mismatch_gauss', side, hybrid, A, B0, seed, scale,
+ * coefs, ...: the same with E = scale * randn(size(B0)) of the matrix-free Gaussian generator (hgm_gauss_create: a
+ * pure function of seed, row and column; never stored).  seed is a non-negative integer below 2^53; the scale
+ * multiplies the coefficients here, one rounding.  Side, hybrid, every size, the coefficients and the lambdas are
+ * checked before a device is touched. */
+static void bounds_mismatch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int gauss) {
     const int side = side_of(prhs[1]);
     const int hybrid = scalar(prhs[2], "hybrid") != 0.0;
     need_double(prhs[3], "A");
     need_double(prhs[4], "B0");
-    need_double(prhs[5], "E");
+    if (!gauss) need_double(prhs[5], "E");
     const int64_t m = (int64_t)mxGetM(prhs[3]), n = (int64_t)mxGetN(prhs[3]);
     if ((int64_t)mxGetM(prhs[4]) != n || (int64_t)mxGetN(prhs[4]) != m)
         fail("hgmres:arg", "hgmres: B0 must be size(A')");
-    if ((int64_t)mxGetM(prhs[5]) != n || (int64_t)mxGetN(prhs[5]) != m)
+    double seedv = 0.0, scale = 1.0;
+    if (gauss) {
+        if (m < 1 || n < 1) fail("hgmres:arg", "hgmres: the Gaussian perturbation needs a non-empty B0");
+        seedv = scalar(prhs[5], "seed");
+        if (!(seedv >= 0.0) || !(seedv <= 9007199254740992.0) || seedv != floor(seedv))
+            fail("hgmres:arg", "hgmres: seed must be a non-negative integer of at most 2^53");
+        scale = scalar(prhs[6], "scale");
+    } else if ((int64_t)mxGetM(prhs[5]) != n || (int64_t)mxGetN(prhs[5]) != m) {
         fail("hgmres:arg", "hgmres: E must be size(B0)");
-    need_double(prhs[6], "coefs");
-    const int64_t nc = (int64_t)mxGetNumberOfElements(prhs[6]);
-    if (mxIsSparse(prhs[6]) || nc < 1 || nc > 64)
-        fail("hgmres:arg", "hgmres: coefs must be a dense vector of 1 to 64 mismatch levels");
-    const double* cf = mxGetDoubles(prhs[6]);
-    for (int64_t j = 0; j < nc; ++j)
-        if (!isfinite(cf[j])) fail("hgmres:arg", "hgmres: every coefficient must be finite");
-    const double* b = vec(prhs[7], m, "b", 0);
-    const double* xt = vec(prhs[8], n, "x_true", 1);
-    const double tol = scalar(prhs[9], "tol");
-    const int maxit = maxit_of(prhs[10]);
-    const double* lam = NULL;
-    if (hybrid) {
-        if (nrhs < 12) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per mismatch level)");
-        need_double(prhs[11], "lambdas");
-        if (mxIsSparse(prhs[11]) || (int64_t)mxGetNumberOfElements(prhs[11]) != nc)
-            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per mismatch level");
-        lam = mxGetDoubles(prhs[11]);
-        for (int64_t j = 0; j < nc; ++j)
-            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
     }
+    const int k = gauss ? 7 : 6;                          /* coefs, b, x_true, tol, maxit [, lambdas] from here */
+    int64_t nc;
+    double* owned;
+    const double* cf = coefs_arg(prhs[k], gauss ? &scale : NULL, &nc, &owned);
+    const double* b = vec(prhs[k + 1], m, "b", 0);
+    const double* xt = vec(prhs[k + 2], n, "x_true", 1);
+    const double tol = scalar(prhs[k + 3], "tol");
+    const int maxit = maxit_of(prhs[k + 4]);
+    const double* lam = hybrid ? lambdas_arg(nrhs, prhs, k + 5, "mismatch level", &nc, NULL) : NULL;
     hgm_mat* A = op(prhs[3], "A");
     check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
     hgm_mat* B0 = op(prhs[4], "B0");
-    hgm_mat* E = op(prhs[5], "E");
-    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nc, mxREAL);
-    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
-    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
-    int* nit = (int*)mxCalloc((size_t)nc, sizeof(int));
-    int* cst = (int*)mxCalloc((size_t)nc, sizeof(int));
-    for (int64_t i = 0; i < n * nc; ++i) mxGetDoubles(X)[i] = (double)NAN;
-    const int st = hgm_gmres_bounds_mismatch(ctx(), NULL, A, B0, E, cf, (int)nc, b, xt, tol, maxit, lam, side, hybrid,
-                                             mxGetDoubles(X), n > 0 ? n : 1, mxGetDoubles(e), mxGetDoubles(r), nit,
-                                             cst);
-    if (st != HGM_E_NOT_ASSIGNED) check(st);             /* unassigned columns are reported in status */
-    mxArray* ni = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
-    mxArray* cs = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
-    for (int64_t j = 0; j < nc; ++j) {
-        mxGetDoubles(ni)[j] = (double)nit[j];
-        mxGetDoubles(cs)[j] = (double)cst[j];
-    }
-    mxFree(nit);
-    mxFree(cst);
-    plhs[0] = X;
-    if (nlhs > 1) plhs[1] = e;
-    if (nlhs > 2) plhs[2] = r;
-    if (nlhs > 3) plhs[3] = ni;
-    if (nlhs > 4) plhs[4] = cs;
-}
-
-/* [X, error_hist, residual_hist, niters, status] = hgmres_mex('gmres_bounds_mismatch_gauss', side, hybrid, A, B0, seed,
- * scale, coefs, b, x_true, tol, maxit [, lambdas]): 'gmres_bounds_mismatch' with E = scale * randn(size(B0)) of the
- * matrix-free Gaussian generator (hgm_gauss_create: a pure function of seed, row and column; never stored).  seed is
- * a non-negative integer below 2^53; the scale multiplies the coefficients here, one rounding.  Everything is checked
- * before a device is touched. */
-static void bounds_mismatch_gauss(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-    const int side = side_of(prhs[1]);
-    const int hybrid = scalar(prhs[2], "hybrid") != 0.0;
-    need_double(prhs[3], "A");
-    need_double(prhs[4], "B0");
-    const int64_t m = (int64_t)mxGetM(prhs[3]), n = (int64_t)mxGetN(prhs[3]);
-    if ((int64_t)mxGetM(prhs[4]) != n || (int64_t)mxGetN(prhs[4]) != m)
-        fail("hgmres:arg", "hgmres: B0 must be size(A')");
-    if (m < 1 || n < 1) fail("hgmres:arg", "hgmres: the Gaussian perturbation needs a non-empty B0");
-    const double seedv = scalar(prhs[5], "seed");
-    if (!(seedv >= 0.0) || !(seedv <= 9007199254740992.0) || seedv != floor(seedv))
-        fail("hgmres:arg", "hgmres: seed must be a non-negative integer of at most 2^53");
-    const double scale = scalar(prhs[6], "scale");
-    need_double(prhs[7], "coefs");
-    const int64_t nc = (int64_t)mxGetNumberOfElements(prhs[7]);
-    if (mxIsSparse(prhs[7]) || nc < 1 || nc > 64)
-        fail("hgmres:arg", "hgmres: coefs must be a dense vector of 1 to 64 mismatch levels");
-    double* cf = (double*)mxCalloc((size_t)nc, sizeof(double));
-    for (int64_t j = 0; j < nc; ++j) {
-        cf[j] = scale == 1.0 ? mxGetDoubles(prhs[7])[j] : mxGetDoubles(prhs[7])[j] * scale;
-        if (!isfinite(cf[j])) fail("hgmres:arg", "hgmres: every coefficient times the scale must be finite");
-    }
-    const double* b = vec(prhs[8], m, "b", 0);
-    const double* xt = vec(prhs[9], n, "x_true", 1);
-    const double tol = scalar(prhs[10], "tol");
-    const int maxit = maxit_of(prhs[11]);
-    const double* lam = NULL;
-    if (hybrid) {
-        if (nrhs < 13) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per mismatch level)");
-        need_double(prhs[12], "lambdas");
-        if (mxIsSparse(prhs[12]) || (int64_t)mxGetNumberOfElements(prhs[12]) != nc)
-            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per mismatch level");
-        lam = mxGetDoubles(prhs[12]);
-        for (int64_t j = 0; j < nc; ++j)
-            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
-    }
-    hgm_mat* A = op(prhs[3], "A");
-    check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
-    hgm_mat* B0 = op(prhs[4], "B0");
+    hgm_mat* E = gauss ? NULL : op(prhs[5], "E");
     hgm_gauss* G = NULL;
-    check(hgm_gauss_create(ctx(), n, m, (uint64_t)seedv, &G));
-    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nc, mxREAL);
-    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
-    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nc, mxREAL);
-    int* nit = (int*)mxCalloc((size_t)nc, sizeof(int));
-    int* cst = (int*)mxCalloc((size_t)nc, sizeof(int));
-    for (int64_t i = 0; i < n * nc; ++i) mxGetDoubles(X)[i] = (double)NAN;
-    const int st = hgm_gmres_bounds_mismatch_gauss(ctx(), NULL, A, B0, G, cf, (int)nc, b, xt, tol, maxit, lam, side,
-                                                   hybrid, mxGetDoubles(X), n, mxGetDoubles(e), mxGetDoubles(r), nit,
-                                                   cst);
+    if (gauss) check(hgm_gauss_create(ctx(), n, m, (uint64_t)seedv, &G));
+    batch_out o = batch_alloc(n, maxit, nc, 2, 1);
+    double *X = mxGetDoubles(o.X), *eh = mxGetDoubles(o.h[0]), *rh = mxGetDoubles(o.h[1]);
+    const int64_t ldx = n > 0 ? n : 1;
+    const int st = gauss ? hgm_gmres_bounds_mismatch_gauss(ctx(), NULL, A, B0, G, cf, (int)nc, b, xt, tol, maxit, lam,
+                                                           side, hybrid, X, ldx, eh, rh, o.nit, o.cst)
+                         : hgm_gmres_bounds_mismatch(ctx(), NULL, A, B0, E, cf, (int)nc, b, xt, tol, maxit, lam, side,
+                                                     hybrid, X, ldx, eh, rh, o.nit, o.cst);
     hgm_gauss_destroy(G);
     if (st != HGM_E_NOT_ASSIGNED) check(st);             /* unassigned columns are reported in status */
-    mxArray* ni = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
-    mxArray* cs = mxCreateDoubleMatrix((mwSize)nc, 1, mxREAL);
-    for (int64_t j = 0; j < nc; ++j) {
-        mxGetDoubles(ni)[j] = (double)nit[j];
-        mxGetDoubles(cs)[j] = (double)cst[j];
-    }
-    mxFree(nit);
-    mxFree(cst);
-    mxFree(cf);
-    plhs[0] = X;
-    if (nlhs > 1) plhs[1] = e;
-    if (nlhs > 2) plhs[2] = r;
-    if (nlhs > 3) plhs[3] = ni;
-    if (nlhs > 4) plhs[4] = cs;
+    if (owned) mxFree(owned);
+    batch_return(&o, nlhs, plhs);
 }
 
 /* [X, error_hist, residual_hist, ar_hist, niters] = hgmres_mex('gk_batch', kind, A, Bm, x_true, tol, maxit [, lambdas]).
@@ -703,56 +675,21 @@ static void gk_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[])
     need_double(prhs[2], "A");
     const int64_t m = (int64_t)mxGetM(prhs[2]), n = (int64_t)mxGetN(prhs[2]);
     need_double(prhs[3], "Bm");
-    int64_t nb = (int64_t)mxGetN(prhs[3]);
+    int64_t nb = (int64_t)mxGetN(prhs[3]), ldb = m > 0 ? m : 1, ldxt;
     if (mxIsSparse(prhs[3]) || (int64_t)mxGetM(prhs[3]) != m || nb < 1 || nb > 64)
         fail("hgmres:arg", "hgmres: Bm must be a dense size(A,1) x nrhs matrix with 1 <= nrhs <= 64");
-    const double* lam = NULL;
-    int64_t ldb = m > 0 ? m : 1;
-    if (hybrid) {
-        if (nrhs < 8) fail("hgmres:arg", "hgmres: the hybrid solvers need lambdas (one per column)");
-        need_double(prhs[7], "lambdas");
-        const int64_t nl = (int64_t)mxGetNumberOfElements(prhs[7]);
-        if (mxIsSparse(prhs[7]) || nl < 1 || nl > 64 || (nl != nb && nb != 1))
-            fail("hgmres:arg", "hgmres: lambdas must be a dense vector with one entry per column");
-        if (nb == 1 && nl > 1) {                          /* one b shared by every lambda */
-            nb = nl;
-            ldb = 0;
-        }
-        lam = mxGetDoubles(prhs[7]);
-        for (int64_t j = 0; j < nb; ++j)
-            if (!(lam[j] >= 0.0) || !isfinite(lam[j])) fail("hgmres:arg", "hgmres: every lambda must be finite and >= 0");
-    }
-    const double* xt = NULL;
-    int64_t ldxt = 0;
-    if (!mxIsEmpty(prhs[4])) {
-        need_double(prhs[4], "x_true");
-        const int64_t xm = (int64_t)mxGetM(prhs[4]), xn = (int64_t)mxGetN(prhs[4]);
-        if (mxIsSparse(prhs[4]) || xm != n || (xn != 1 && xn != nb))
-            fail("hgmres:arg", "hgmres: x_true must be dense, size(A,2) x 1 or size(A,2) x nrhs, or []");
-        xt = mxGetDoubles(prhs[4]);
-        ldxt = xn == 1 && nb != 1 ? 0 : n;
-    }
+    const double* lam = hybrid ? lambdas_arg(nrhs, prhs, 7, "column", &nb, &ldb) : NULL;
+    const double* xt = x_true_cols(prhs[4], n, nb, &ldxt);
     const double tol = scalar(prhs[5], "tol");
     const int maxit = maxit_of(prhs[6]);
     hgm_mat* A = op(prhs[2], "A");
     check(hgm_ctx_set_option(ctx(), HGM_OPT_PARITY, 0.0));
     hgm_mat* At = transpose_op(A);
-    mxArray* X = mxCreateDoubleMatrix((mwSize)n, (mwSize)nb, mxREAL);
-    mxArray* e = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
-    mxArray* r = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
-    mxArray* a = mxCreateDoubleMatrix((mwSize)maxit, (mwSize)nb, mxREAL);
-    int* nit = (int*)mxCalloc((size_t)nb, sizeof(int));
-    for (int64_t i = 0; i < n * nb; ++i) mxGetDoubles(X)[i] = (double)NAN;
-    check(hgm_gk_batch(ctx(), NULL, A, At, mxGetDoubles(prhs[3]), ldb, (int)nb, xt, ldxt, tol, maxit, lam, kind,
-                       hybrid, mxGetDoubles(X), n > 0 ? n : 1, mxGetDoubles(e), mxGetDoubles(r), mxGetDoubles(a), nit));
-    mxArray* ni = mxCreateDoubleMatrix((mwSize)nb, 1, mxREAL);
-    for (int64_t j = 0; j < nb; ++j) mxGetDoubles(ni)[j] = (double)nit[j];
-    mxFree(nit);
-    plhs[0] = X;
-    if (nlhs > 1) plhs[1] = e;
-    if (nlhs > 2) plhs[2] = r;
-    if (nlhs > 3) plhs[3] = a;
-    if (nlhs > 4) plhs[4] = ni;
+    batch_out o = batch_alloc(n, maxit, nb, 3, 0);
+    check(hgm_gk_batch(ctx(), NULL, A, At, mxGetDoubles(prhs[3]), ldb, (int)nb, xt, ldxt, tol, maxit, lam, kind, hybrid,
+                       mxGetDoubles(o.X), n > 0 ? n : 1, mxGetDoubles(o.h[0]), mxGetDoubles(o.h[1]),
+                       mxGetDoubles(o.h[2]), o.nit));
+    batch_return(&o, nlhs, plhs);
 }
 
 /* [sigma, resid, utb, steps_done, VtX, Phi, nconv, U, V] = hgmres_mex('svds_gk', A, b, steps, nsv [, X]).  Every size
@@ -848,10 +785,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         gk_batch(nlhs, plhs, nrhs, prhs);
     } else if (!strcmp(fn, "gmres_bounds_mismatch")) {
         nargs(nrhs, 10, 11, fn);
-        bounds_mismatch(nlhs, plhs, nrhs, prhs);
+        bounds_mismatch(nlhs, plhs, nrhs, prhs, 0);
     } else if (!strcmp(fn, "gmres_bounds_mismatch_gauss")) {
         nargs(nrhs, 11, 12, fn);
-        bounds_mismatch_gauss(nlhs, plhs, nrhs, prhs);
+        bounds_mismatch(nlhs, plhs, nrhs, prhs, 1);
     } else if (!strcmp(fn, "svds_gk")) {
         nargs(nrhs, 4, 5, fn);
         svds_gk(nlhs, plhs, nrhs, prhs);

@@ -6,6 +6,7 @@
 * the batch against the oracle's four ``*_bounds`` solvers called once per column, at the project's
   bar 1e-10, with a stopping tolerance at which columns leave the batch at different iterations;
 * the batch against itself, bitwise: one batch = its columns run alone, across repacked groups;
+* the batch on operators in a stored pixel order against the reference-order pair, one x_true per column;
 * breakdown inside a batch, refusals, and the noise-level pipeline and gateway command on top.
 """
 import ctypes as C
@@ -21,6 +22,7 @@ from hgmres import _lib as L
 from hgmres import analysis
 from hgmres.regtools import generate_test_problem
 from oracle import restatement as R   # checker only
+from tiled_pair import tiled_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -317,6 +319,36 @@ def test_shared_x_true_equals_repeated_column(gpu_ctx, problems):
     c = hgmres.gmres_bounds_batch(P["Ao"], P["Bo"], P["Bm"], None, STOP, MAXIT, "ba", lambdas=LAMS, ctx=gpu_ctx)
     assert np.all(np.isnan(c.error_norm))
     assert np.array_equal(c.x, a.x) and np.array_equal(c.residual_norm, a.residual_norm, equal_nan=True)
+
+
+@pytest.fixture(scope="module")
+def tiled(gpu_ctx):
+    return tiled_pair(gpu_ctx)
+
+
+@pytest.mark.parametrize("side,hybrid", [("ab", True), ("ba", False)])
+def test_batch_on_tiled_operators(gpu_ctx, tiled, side, hybrid):
+    """The batch on operators with a stored pixel order against the same pair in the reference order, b, x_true
+    and x in the reference order: three different x_true columns, so a permutation into the stored order that
+    reaches the wrong column, or none, is an O(1) error in that column's error history; x comes back through
+    the inverse permutation."""
+    P = tiled["P"]
+    xt = np.asarray(P.x_true, dtype=np.float64).ravel()
+    Bm = noisy_rhs(np.asarray(P.b, dtype=np.float64).ravel(), LEVELS[[0, 2, 4]])
+    XT = xt[:, None] * np.array([1.0, 0.5, -1.0])[None, :]
+    lam = LAMS[:3] if hybrid else None
+    run = lambda A, B, x_true: hgmres.gmres_bounds_batch(A, B, Bm, x_true, 0.0, 8, side, lambdas=lam, ctx=gpu_ctx,
+                                                         return_H=True)
+    for x_true in (XT, xt):                                  # one x_true per column, then one shared
+        Rt, Rr = run(tiled["At"], tiled["Bt"], x_true), run(tiled["Ar"], tiled["Br"], x_true)
+        assert np.array_equal(Rt.niters, Rr.niters) and np.all(Rt.niters == 8)
+        for j in range(3):
+            assert rel(Rt.x[:, j], Rr.x[:, j]) <= TOL
+            hist_ok(Rt.residual_norm[:, j], Rr.residual_norm[:, j], TOL)
+            hist_ok(Rt.error_norm[:, j], Rr.error_norm[:, j], TOL)
+            assert np.max(np.abs(Rt.H[j] - Rr.H[j])) <= TOL * np.max(np.abs(Rr.H[j]))
+        if x_true is XT:   # the columns' x_true are told apart: far more than the bar between their histories
+            assert min(rel(Rr.error_norm[:, 1], Rr.error_norm[:, 0]), rel(Rr.error_norm[:, 2], Rr.error_norm[:, 0])) > 1e-3
 
 
 # ---------------------------------------------------------------------------------------------

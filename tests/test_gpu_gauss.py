@@ -24,6 +24,7 @@ from hgmres import analysis
 from hgmres.problems import gaussian_entries, tomo_problem
 from hgmres.regtools import generate_test_problem
 from oracle import restatement as R   # checker only
+from tiled_pair import tiled_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -306,20 +307,14 @@ def test_frobenius_norm(gpu_ctx, rows, cols):
 # ---------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def tiled(gpu_ctx):
-    """A 32^2 / 16-angle pair stored in 4 x 4 tiles and 16 x 16 super-blocks (as test_gpu_mismatch.py's
-    test_spmm_pert_tiled_pair builds its pair) and the same pair in the reference order."""
-    P = tomo_problem(32, 16, noise=1e-2, seed=0, backprojector="pixel")
-    A, B = sp.csr_matrix(P.A), sp.csr_matrix(P.B)
-    A.sort_indices()
-    B.sort_indices()
-    At = hgmres.SparseOperator.from_scipy_tiled(A, 32, 4, 16, ctx=gpu_ctx)
-    Bt = hgmres.SparseOperator.from_scipy_tiled(sp.csr_matrix(B.T), 32, 4, 16, ctx=gpu_ctx).T
+    """The tiled and the reference-order pair of tiled_pair.py, and B with its values zeroed in both orders."""
+    T = tiled_pair(gpu_ctx)
+    B = T["B"]
     Bz = sp.csr_matrix((np.zeros(B.nnz), B.indices.copy(), B.indptr.copy()), shape=B.shape)   # B's pattern, zeros
     Bzt = hgmres.SparseOperator.from_scipy_tiled(sp.csr_matrix((np.zeros(B.nnz), B.T.tocsr().indices, B.T.tocsr().indptr),
                                                                shape=B.T.shape), 32, 4, 16, ctx=gpu_ctx).T
-    assert Bt.pixel_order("rows")[1:] == (4, 16) and Bzt.pixel_order("rows")[1:] == (4, 16)
-    up = lambda M: hgmres.SparseOperator.from_scipy(M, ctx=gpu_ctx)
-    return dict(P=P, A=A, B=B, At=At, Bt=Bt, Bzt=Bzt, Ar=up(A), Br=up(B), Bzr=up(Bz))
+    assert Bzt.pixel_order("rows")[1:] == (4, 16)
+    return dict(T, Bzt=Bzt, Bzr=hgmres.SparseOperator.from_scipy(Bz, ctx=gpu_ctx))
 
 
 def test_spmm_pert_gauss_on_a_tiled_operator(gpu_ctx, tiled):

@@ -6,7 +6,8 @@ kernel (hgm_mv_axpby_norms, csrc/gkmv.hip), on the device.
   the vector count, the slot and the neighbours;
 * the batch against the oracle's four Golub-Kahan solvers called once per column, at the project's
   Golub-Kahan bar (test_gpu_parity._gkb_check), with stopping tolerances at which columns leave the
-  batch at different iterations, and against the library's single solvers at the same bar;
+  batch at different iterations, and against the library's single solvers at the same bar; on an operator in
+  a stored pixel order against the reference-order one at that bar, one x_true per column;
 * the batch against itself, bitwise: one batch = its columns run alone, across re-gathered groups;
 * b = 0 columns, maxit = 1, refusals, the equivalence pipeline and the gateway command on top.
 """
@@ -25,6 +26,7 @@ from hgmres import analysis
 from oracle import restatement as R   # checker only
 from test_gpu_batch import LAMS, LEVELS, MAXIT, NRHS, noisy_rhs
 from test_gpu_parity import TOL, _Rounded, _gkb_check, rel
+from tiled_pair import tiled_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -250,6 +252,38 @@ def test_gk_batch_matches_single_solver(gpu_ctx, problems, kind, name):
         assert Rb.niters[j] == s[-1], (j, Rb.niters[j], s[-1])
         fn = _oracle_fn(kind, P["Bm"][:, j], P["xt"], tol, MAXIT, LAMS[j])
         _close_as_the_oracle(_hists(Rb, kind, j), s, fn, P["A"], NHIST[kind], f"{kind} {name} col {j}")
+
+
+@pytest.fixture(scope="module")
+def tiled(gpu_ctx):
+    return tiled_pair(gpu_ctx)
+
+
+@pytest.mark.parametrize("kind", ["lsqr", "hybrid_lsmr"])
+def test_gk_batch_on_tiled_operators(gpu_ctx, tiled, kind):
+    """The batch on A in a stored pixel order (At its device transpose) against A in the reference order, b,
+    x_true and x in the reference order, at the bar of the batch against the single solver with the
+    reference-order run for `single` and the oracle on the reference-order matrix.  Three different x_true
+    columns: a permutation into the stored order that reaches the wrong column, or none, is an O(1) error in that
+    column's error history.  lsqr updates x in place, hybrid_lsmr forms x = V_k y; then one shared b (ldb = 0)
+    with three lambdas for the hybrid kind."""
+    P = tiled["P"]
+    hybrid = KINDS[kind][3]
+    xt = np.asarray(P.x_true, dtype=np.float64).ravel()
+    Bm = noisy_rhs(np.asarray(P.b, dtype=np.float64).ravel(), LEVELS[[0, 2, 4]])
+    XT = xt[:, None] * np.array([1.0, 0.5, -1.0])[None, :]
+    lam = LAMS[:3] if hybrid else None
+    maxit = 8
+    for rhs in (Bm, Bm[:, 1]) if hybrid else (Bm,):          # one b per column, then one shared
+        run = lambda Aop: hgmres.gk_batch(Aop, rhs, XT, 0.0, maxit, kind, lambdas=lam, ctx=gpu_ctx)
+        Rt, Rr = run(tiled["At"]), run(tiled["Ar"])
+        assert Rt.x.shape == (xt.size, 3)
+        assert np.array_equal(Rt.niters, Rr.niters) and np.all(Rt.niters == maxit)
+        for j in range(3):
+            bj = rhs if rhs.ndim == 1 else rhs[:, j]
+            fn = _oracle_fn(kind, bj, XT[:, j], 0.0, maxit, LAMS[j])
+            _close_as_the_oracle(_hists(Rt, kind, j), _hists(Rr, kind, j), fn, tiled["A"], NHIST[kind],
+                                 f"{kind} tiled {'shared b' if rhs.ndim == 1 else 'columns'} col {j}")
 
 
 # ---------------------------------------------------------------------------------------------
