@@ -233,13 +233,14 @@ void basis_project(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq
     for (int c0 = 0; c0 < nx; c0 += BP_G) {
         const int ng = nx - c0 < BP_G ? nx - c0 : BP_G;
         const double* Xg = X + (int64_t)c0 * ldx;
-        auto go = [&](auto kern, int njb) {
-            const dim3 grid((unsigned)nb, (unsigned)((k + 16 * njb - 1) / (16 * njb)));
-            kern<<<grid, BS, 0, c->stream>>>(rows, k, Q, ldq, ng, Xg, ldx, parts);
-        };
-        if (k <= 16) go(k_basis_project<1>, 1);
-        else if (k <= 32) go(k_basis_project<2>, 2);
-        else go(k_basis_project<4>, BP_JC / 16);
+        // 16-column MFMA blocks of the basis per workgroup: the fewest that hold k, BP_JC / 16 at most
+        using ProjectBlocks = Ints<1, 2, BP_JC / 16>;
+        dispatch(
+            [&](auto njb) {
+                const dim3 grid((unsigned)nb, (unsigned)((k + 16 * njb - 1) / (16 * njb)));
+                k_basis_project<njb><<<grid, BS, 0, c->stream>>>(rows, k, Q, ldq, ng, Xg, ldx, parts);
+            },
+            ProjectBlocks{k <= 16 ? 1 : k <= 32 ? 2 : BP_JC / 16});
         k_ba_finalize<<<ng * k, BS, 0, c->stream>>>(parts, nb, C_dev + (size_t)c0 * k);
     }
     HGM_HIP(hipGetLastError());
@@ -261,23 +262,16 @@ void basis_rotate(hgm_ctx* c, int64_t rows, int k, const double* Q, int64_t ldq,
     const size_t lds = sizeof(double) * (size_t)lc * br_lds_stride(k);
     hipEvent_t tm;
     timing_begin(c, KC_BASIS, &tm);
-    auto go = [&](auto kern) { kern<<<grid, BS, lds, c->stream>>>(rows, k, Q, ldq, Y, ldy, p, lc, W, ldw, parts); };
-    auto pick = [&](auto sums) {
-        constexpr bool S = decltype(sums)::value;
-        if (k <= 4) go(k_basis_rotate<1, S>);
-        else if (k <= 8) go(k_basis_rotate<2, S>);
-        else if (k <= 16) go(k_basis_rotate<4, S>);
-        else if (k <= 32) go(k_basis_rotate<8, S>);
-        else if (k <= 64) go(k_basis_rotate<16, S>);
-        else if (k <= 96) go(k_basis_rotate<24, S>);
-        else go(k_basis_rotate<0, S>);
-    };
-    if (sumsq_dev) {
-        pick(std::true_type{});
-        k_ba_finalize<<<p, BS, 0, c->stream>>>(parts, nb, sumsq_dev);
-    } else {
-        pick(std::false_type{});
-    }
+    // KQ of the kernel: the smallest instantiated register count with k <= 4 KQ, else 0 (operands re-read)
+    using RotateSteps = Ints<1, 2, 4, 8, 16, 24, 0>;
+    const int kq = k <= 4 ? 1 : k <= 8 ? 2 : k <= 16 ? 4 : k <= 32 ? 8 : k <= 64 ? 16 : k <= 96 ? 24 : 0;
+    dispatch(
+        [&](auto kqv, auto sums) {
+            constexpr bool S = sums;
+            k_basis_rotate<kqv, S><<<grid, BS, lds, c->stream>>>(rows, k, Q, ldq, Y, ldy, p, lc, W, ldw, parts);
+        },
+        RotateSteps{kq}, flag(sumsq_dev != nullptr));
+    if (sumsq_dev) k_ba_finalize<<<p, BS, 0, c->stream>>>(parts, nb, sumsq_dev);
     HGM_HIP(hipGetLastError());
     timing_end(c, KC_BASIS, tm, 8.0 * (double)rows * ((double)k * grid.y + p));
 }

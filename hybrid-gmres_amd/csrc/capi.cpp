@@ -884,7 +884,7 @@ HGM_API int hgm_mat_info(const hgm_mat* M, int64_t* rows, int64_t* cols, int64_t
 
 HGM_API int hgm_mat_set_bands(hgm_ctx* c, hgm_mat* M, int64_t band_width, int group) {
     if (!c || !M || band_width < -1) return HGM_E_ARG;
-    if (group != 0 && group != 4 && group != 8 && group != 16 && group != 32 && group != 64) return HGM_E_ARG;
+    if (group != 0 && !BandGroups::has(group)) return HGM_E_ARG;
     HGM_TRY(c, {
         HGM_HIP(hipSetDevice(c->device));
         set_bands(c, M, band_width == -1 ? auto_band_width(M) : band_width);
@@ -896,8 +896,8 @@ HGM_API int hgm_mat_set_bands(hgm_ctx* c, hgm_mat* M, int64_t band_width, int gr
 
 HGM_API int hgm_mat_tune(hgm_mat* M, int variant, int group) {
     if (!M || variant < 0 || variant > 31) return HGM_E_ARG;
-    if (group != 0 && group != 2 && group != 4 && group != 8 && group != 16 && group != 32 && group != 64) return HGM_E_ARG;
-    if (group == 2 && !(variant & SPMV_STREAM)) return HGM_E_ARG;   // (2 lanes: streaming reduction only)
+    // lanes of the kernel the variant selects (2 lanes: streaming reduction only); 0 keeps them
+    if (group != 0 && !((variant & SPMV_STREAM) ? StreamGroups::has(group) : RowGroups::has(group))) return HGM_E_ARG;
     if ((variant & SPMV_PAGED) && !M->pg_ptr) {   // page index on demand (over the current stream)
         HGM_TRY(M->ctx, {
             HGM_HIP(hipSetDevice(M->ctx->device));

@@ -206,16 +206,11 @@ void gauss_mm(hgm_ctx* c, const hgm_gauss* G, const PixOrder& row_order, int nve
     GaussCoef cf;
     for (int r = 0; r < SPMM_MAXV; ++r) cf.c[r] = r < nvec ? (coefs ? coefs[r] : 1.0) : 0.0;
     const dim3 g((unsigned)nb), b(BS);
-#define HGM_GAUSS_NV(N)                                                                                     \
-    if (accumulate) launch(c, false, k_gauss_mm<N, 1>, g, b, G->rows, G->cols, G->seed, row_order, cf, Xi, Yi); \
-    else launch(c, false, k_gauss_mm<N, 0>, g, b, G->rows, G->cols, G->seed, row_order, cf, Xi, Yi);
-    switch (spmm_width(nvec)) {
-        case 1: HGM_GAUSS_NV(1) break;
-        case 2: HGM_GAUSS_NV(2) break;
-        case 4: HGM_GAUSS_NV(4) break;
-        default: HGM_GAUSS_NV(8) break;
-    }
-#undef HGM_GAUSS_NV
+    dispatch(
+        [&](auto nv, auto acc) {
+            launch(c, false, k_gauss_mm<nv, acc>, g, b, G->rows, G->cols, G->seed, row_order, cf, Xi, Yi);
+        },
+        MvWidths{spmm_width(nvec)}, flag(accumulate));
     HGM_HIP(hipGetLastError());
 }
 

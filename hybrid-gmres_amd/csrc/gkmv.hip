@@ -262,13 +262,8 @@ static void mv_finish_sums(hgm_ctx* c, int64_t n, int NV, int sum, const double*
     launch(c, false, k_mv_finalize, dim3(NV), dim3(BS), parts, np, sums);
 }
 
-#define HGM_GKMV_NV(nvec, ...) \
-    switch (spmm_width(nvec)) { \
-        case 1: { constexpr int N = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int N = 2; __VA_ARGS__; } break; \
-        case 4: { constexpr int N = 4; __VA_ARGS__; } break; \
-        default: { constexpr int N = 8; __VA_ARGS__; } break; \
-    }
+static MvWidths width_of(int nvec) { return MvWidths{spmm_width(nvec)}; }
+using LinTerms = Ints<1, 2, 3>;   // terms of mv_lin's linear form
 
 void mv_lin(hgm_ctx* c, int64_t n, int nvec, const MvLin& L) {
     check_nvec(nvec);
@@ -280,11 +275,8 @@ void mv_lin(hgm_ctx* c, int64_t n, int nvec, const MvLin& L) {
     if (n > 0) {
         MvLinArgs A{L.X, L.Y, L.Z, L.D, L.Out, L.a, L.b, L.c};
         const dim3 g(np), b(BS);
-        HGM_GKMV_NV(nvec, {
-            if (L.nterms == 1) launch(c, false, k_mv_lin<N, 1>, g, b, n, A, L.sum, parts);
-            else if (L.nterms == 2) launch(c, false, k_mv_lin<N, 2>, g, b, n, A, L.sum, parts);
-            else launch(c, false, k_mv_lin<N, 3>, g, b, n, A, L.sum, parts);
-        })
+        dispatch([&](auto nv, auto nt) { launch(c, false, k_mv_lin<nv, nt>, g, b, n, A, L.sum, parts); }, width_of(nvec),
+                 LinTerms{L.nterms});
     }
     mv_finish_sums(c, n, spmm_width(nvec), L.sum, parts, np, L.sums);
     HGM_HIP(hipGetLastError());
@@ -294,7 +286,7 @@ void mv_div(hgm_ctx* c, int64_t n, int nvec, const double* In, double* Out, cons
     check_nvec(nvec);
     if (n <= 0) return;
     const dim3 g(gkmv_grid(n)), b(BS);
-    HGM_GKMV_NV(nvec, launch(c, false, k_mv_div<N>, g, b, n, In, Out, s, guard ? 1 : 0))
+    dispatch([&](auto nv) { launch(c, false, k_mv_div<nv>, g, b, n, In, Out, s, guard ? 1 : 0); }, width_of(nvec));
     HGM_HIP(hipGetLastError());
 }
 
@@ -305,7 +297,8 @@ void mv_lsqr_step(hgm_ctx* c, int64_t n, int nvec, double* V, double* X, double*
     double* parts = sum != MVS_NONE ? c->buf<double>("gkmv_parts", (size_t)SPMM_MAXV * MAX_PARTS) : nullptr;
     if (n > 0) {
         const dim3 g(np), b(BS);
-        HGM_GKMV_NV(nvec, launch(c, false, k_mv_lsqr_step<N>, g, b, n, V, X, W, alpha, cx, cw, sum, D, parts))
+        dispatch([&](auto nv) { launch(c, false, k_mv_lsqr_step<nv>, g, b, n, V, X, W, alpha, cx, cw, sum, D, parts); },
+                 width_of(nvec));
     }
     mv_finish_sums(c, n, spmm_width(nvec), sum, parts, np, sums);
     HGM_HIP(hipGetLastError());
@@ -319,8 +312,12 @@ void mv_lsmr_step(hgm_ctx* c, int64_t n, int nvec, double* V, double* X, double*
     double* parts = sum != MVS_NONE ? c->buf<double>("gkmv_parts", (size_t)SPMM_MAXV * MAX_PARTS) : nullptr;
     if (n > 0) {
         const dim3 g(np), b(BS);
-        HGM_GKMV_NV(nvec, launch(c, false, k_mv_lsmr_step<N>, g, b, n, V, X, H, HB, alpha, chb, cx, ch,
-                                 first ? 1 : 0, sum, D, parts))
+        dispatch(
+            [&](auto nv) {
+                launch(c, false, k_mv_lsmr_step<nv>, g, b, n, V, X, H, HB, alpha, chb, cx, ch, first ? 1 : 0, sum, D,
+                       parts);
+            },
+            width_of(nvec));
     }
     mv_finish_sums(c, n, spmm_width(nvec), sum, parts, np, sums);
     HGM_HIP(hipGetLastError());
@@ -330,10 +327,8 @@ void mv_regather(hgm_ctx* c, int64_t n, int nvec, const MvSlots& src, double* Ou
     check_nvec(nvec);
     if (n <= 0) return;
     const dim3 g(gkmv_grid(n)), b(BS);
-    HGM_GKMV_NV(nvec, launch(c, false, k_mv_regather<N>, g, b, n, src, Out))
+    dispatch([&](auto nv) { launch(c, false, k_mv_regather<nv>, g, b, n, src, Out); }, width_of(nvec));
     HGM_HIP(hipGetLastError());
 }
-
-#undef HGM_GKMV_NV
 
 }  // namespace hgm

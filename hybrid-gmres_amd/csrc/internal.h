@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "dispatch.h"
 #include "hgmres.h"
 
 // Measured variants of the one-pass kernel (the kind-0 sub-chunk pass, row-pair modes 1-3, other
@@ -338,6 +339,11 @@ struct PendNorm {
 };
 
 int pick_group(int64_t rows, int64_t nnz);
+// Lanes per row / segment the SpMV kernels are instantiated for (dispatch.h); hgm_mat_tune and
+// hgm_mat_set_bands accept exactly these.  Two lanes: the streaming reduction only.
+using RowGroups = Ints<64, 32, 16, 8, 4>;          // hgm_mat::group: k_spmv, k_spmm, k_spmm_pert
+using BandGroups = Ints<64, 32, 16, 8, 4>;         // hgm_mat::bgroup: k_spmv_band
+using StreamGroups = Ints<64, 32, 16, 8, 2, 4>;    // hgm_mat::sgroup / bsgroup: k_spmv_stream
 // y = epi(M x): EPI_ADD: t + a*z ; EPI_SUB: t - a*z ; EPI_RSUB: z - t  (two roundings, no FMA)
 // sumsq_out (optional, device): also *sumsq_out = sum_r y_r^2 (fused into the row kernel)
 template <typename T>
@@ -411,6 +417,7 @@ struct MvCols {
     double* p[SPMM_MAXV];
 };
 int spmm_width(int nvec);
+using MvWidths = Ints<1, 2, 4, 8>;   // the values of spmm_width: every multi-vector kernel's NV
 void mv_pack(hgm_ctx* c, int64_t n, int nvec, const MvCols& src, double* Xi);
 void mv_unpack(hgm_ctx* c, int64_t n, int nvec, const double* Yi, const MvCols& dst, bool last = false);
 void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi);

@@ -657,15 +657,11 @@ static bool mgs_single(hgm_ctx* c, int64_t n, T* Q, int64_t ldq, int kk, T* Hcol
     if (!krylov_padded(c, ldq) || n > ldq) return false;
     T* v = Q + (int64_t)(kk + 1) * ldq;
     hipStream_t st = c->stream;
-    switch (ldq / MGS1_BS) {
-    case 4: k_mgs_single<T, 4><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); break;
-    case 8: k_mgs_single<T, 8><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); break;
-    case 12: k_mgs_single<T, 12><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); break;
-    case 16: k_mgs_single<T, 16><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); break;
-    case 20: k_mgs_single<T, 20><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); break;
-    case 24: k_mgs_single<T, 24><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); break;
-    default: return false;
-    }
+    // elements per thread: krylov_ld pads short columns to multiples of 4 * MGS1_BS
+    using SingleWidths = Ints<4, 8, 12, 16, 20, 24>;
+    if (!dispatch([&](auto w) { k_mgs_single<T, w><<<1, MGS1_BS, 0, st>>>((int)n, Q, ldq, src, v, kk, Hcol); },
+                  SingleWidths{(int)(ldq / MGS1_BS), false}))
+        return false;
     HGM_HIP(hipGetLastError());
     return true;
 }
@@ -1221,14 +1217,13 @@ void mgs(hgm_ctx* c, int64_t n, T* Q, int64_t ldq, int kk, T* Hcol, bool dist, c
         T* Gt = c->buf<T>("mgs1_G", (size_t)MGS1_MAXC * MGS1_MAXC / 2 + MGS1_MAXC);
         T* hdev = c->buf<T>("mgs1_h", MGS1_MAXC + 2);
         const size_t lds = sizeof(T) * ((size_t)kk * (kk + 1) / 2 + 1);
-#define HGM_MGS1_P(PV, STMT) \
-    if (P == PV) {          \
-        constexpr int PT = PV; \
-        STMT;               \
-    }
-#define HGM_MGS1_PS(STMT) HGM_MGS1_P(1, STMT) else HGM_MGS1_P(2, STMT) else HGM_MGS1_P(4, STMT) else HGM_REQUIRE(false, "mgs1: tile width")
-        HGM_MGS1_PS((k_mgs1_dots<T, PT><<<npr + s1.blocks(), BS, 0, st>>>(n, Q, ldq, kk, src, npr, pr, pg, s1, pend_h, xe,
-                                                                          cp_src, cp_dst)));
+        // f(tile width as a constant): the dots and update kernels are instantiated per width
+        using Mgs1Tiles = Ints<1, 2, 4>;
+        auto tiled = [&](auto f) { HGM_REQUIRE(dispatch(f, Mgs1Tiles{P, false}), "mgs1: tile width"); };
+        tiled([&](auto pt) {
+            k_mgs1_dots<T, pt><<<npr + s1.blocks(), BS, 0, st>>>(n, Q, ldq, kk, src, npr, pr, pg, s1, pend_h, xe, cp_src,
+                                                                 cp_dst);
+        });
         const int nb = npr;
         T* pout = c->buf<T>("mgs_parts", 2 * MAX_PARTS);
         const bool fused = !dist && c->num.mgs_fused;
@@ -1239,8 +1234,10 @@ void mgs(hgm_ctx* c, int64_t n, T* Q, int64_t ldq, int kk, T* Hcol, bool dist, c
             fz.npr = npr;
             fz.Gt = Gt;
             fz.ngx = xe ? 2 : 0;
-            HGM_MGS1_PS((k_mgs1_update<T, true, PT><<<nb + s2.blocks(), BS, lds, st>>>(
-                n, nb, Q, ldq, kk, src, v, hdev, Hcol, pout, s2, pend_h, nullptr, nullptr, xe ? qg : nullptr, fz)));
+            tiled([&](auto pt) {
+                k_mgs1_update<T, true, pt><<<nb + s2.blocks(), BS, lds, st>>>(
+                    n, nb, Q, ldq, kk, src, v, hdev, Hcol, pout, s2, pend_h, nullptr, nullptr, xe ? qg : nullptr, fz);
+            });
         } else if (dist) {
             T* redd = c->buf<T>("mgs1_red", 2 * MGS1_MAXC + 2);
             k_mgs1_solve<T, 1><<<1, MGS1_SBS, 0, st>>>(kk, pr, pg, npr, redd, Gt, hdev, nullptr);
@@ -1250,12 +1247,12 @@ void mgs(hgm_ctx* c, int64_t n, T* Q, int64_t ldq, int kk, T* Hcol, bool dist, c
             k_mgs1_solve<T, 0><<<1, MGS1_SBS, lds, st>>>(kk, pr, pg, npr, nullptr, Gt, hdev, gx);
         }
         if (!fused) {
-            HGM_MGS1_PS((k_mgs1_update<T, false, PT><<<nb + s2.blocks(), BS, 0, st>>>(
-                n, nb, Q, ldq, kk, src, v, hdev, Hcol, pout, s2, pend_h, Gt + (size_t)kk * (kk - 1) / 2, gx,
-                xe ? qg : nullptr, fz)));
+            tiled([&](auto pt) {
+                k_mgs1_update<T, false, pt><<<nb + s2.blocks(), BS, 0, st>>>(
+                    n, nb, Q, ldq, kk, src, v, hdev, Hcol, pout, s2, pend_h, Gt + (size_t)kk * (kk - 1) / 2, gx,
+                    xe ? qg : nullptr, fz);
+            });
         }
-#undef HGM_MGS1_PS
-#undef HGM_MGS1_P
         if (defer && !dist && kk + 2 <= MGS1_MAXC) {   // the next step must be one-reduction too
             // the next step's SpMVs divide by H(kk+1,kk) in their epilogues
             HGM_HIP(hipGetLastError());

@@ -156,12 +156,7 @@ void mv_pack(hgm_ctx* c, int64_t n, int nvec, const MvCols& src, double* Xi) {
     HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, "mv_pack: 1 <= nvec <= 8");
     if (n <= 0) return;
     const dim3 g(mv_grid(n)), b(BS);
-    switch (spmm_width(nvec)) {
-        case 1: launch(c, false, k_pack<1>, g, b, n, nvec, src, Xi); break;
-        case 2: launch(c, false, k_pack<2>, g, b, n, nvec, src, Xi); break;
-        case 4: launch(c, false, k_pack<4>, g, b, n, nvec, src, Xi); break;
-        default: launch(c, false, k_pack<8>, g, b, n, nvec, src, Xi); break;
-    }
+    dispatch([&](auto nv) { launch(c, false, k_pack<nv>, g, b, n, nvec, src, Xi); }, MvWidths{spmm_width(nvec)});
     HGM_HIP(hipGetLastError());
 }
 
@@ -169,32 +164,8 @@ void mv_unpack(hgm_ctx* c, int64_t n, int nvec, const double* Yi, const MvCols& 
     HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, "mv_unpack: 1 <= nvec <= 8");
     if (n <= 0) return;
     const dim3 g(mv_grid(n)), b(BS);
-    switch (spmm_width(nvec)) {
-        case 1: launch(c, last, k_unpack<1>, g, b, n, nvec, Yi, dst); break;
-        case 2: launch(c, last, k_unpack<2>, g, b, n, nvec, Yi, dst); break;
-        case 4: launch(c, last, k_unpack<4>, g, b, n, nvec, Yi, dst); break;
-        default: launch(c, last, k_unpack<8>, g, b, n, nvec, Yi, dst); break;
-    }
+    dispatch([&](auto nv) { launch(c, last, k_unpack<nv>, g, b, n, nvec, Yi, dst); }, MvWidths{spmm_width(nvec)});
     HGM_HIP(hipGetLastError());
-}
-
-template <int NV>
-static void launch_spmm(hgm_ctx* c, const hgm_mat* M, const double* Xi, double* Yi) {
-    const double* val = reinterpret_cast<const double*>(M->val);
-#define HGM_SPMM_G(GV)                                                                                         \
-    {                                                                                                          \
-        const int64_t nb = (M->rows + (BS / GV) - 1) / (BS / GV);                                              \
-        HGM_REQUIRE(nb <= 0x7fffffff, "spmm: too many rows for one launch");                                   \
-        launch(c, false, k_spmm<NV, GV>, dim3((unsigned)nb), dim3(BS), M->rows, M->rp, M->ci, val, Xi, Yi);    \
-    }
-    switch (M->group) {
-        case 64: HGM_SPMM_G(64) break;
-        case 32: HGM_SPMM_G(32) break;
-        case 16: HGM_SPMM_G(16) break;
-        case 8: HGM_SPMM_G(8) break;
-        default: HGM_SPMM_G(4) break;
-    }
-#undef HGM_SPMM_G
 }
 
 void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi) {
@@ -202,12 +173,14 @@ void spmm(hgm_ctx* c, const hgm_mat* M, int nvec, const double* Xi, double* Yi) 
     HGM_REQUIRE(nvec >= 1 && nvec <= SPMM_MAXV, "spmm: 1 <= nvec <= 8");
     HGM_REQUIRE(M->cols <= 0x7fffffff, "spmm: 32-bit column indices");
     if (M->rows <= 0) return;
-    switch (spmm_width(nvec)) {
-        case 1: launch_spmm<1>(c, M, Xi, Yi); break;
-        case 2: launch_spmm<2>(c, M, Xi, Yi); break;
-        case 4: launch_spmm<4>(c, M, Xi, Yi); break;
-        default: launch_spmm<8>(c, M, Xi, Yi); break;
-    }
+    const double* val = reinterpret_cast<const double*>(M->val);
+    dispatch(
+        [&](auto nv, auto g) {
+            const int64_t nb = (M->rows + (BS / g) - 1) / (BS / g);
+            HGM_REQUIRE(nb <= 0x7fffffff, "spmm: too many rows for one launch");
+            launch(c, false, k_spmm<nv, g>, dim3((unsigned)nb), dim3(BS), M->rows, M->rp, M->ci, val, Xi, Yi);
+        },
+        MvWidths{spmm_width(nvec)}, RowGroups{M->group});
     HGM_HIP(hipGetLastError());
 }
 
@@ -373,28 +346,6 @@ bool same_pattern(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E) {
     return h == 0.0;
 }
 
-template <int NV, int SHARED>
-static void launch_spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, const PertCoef& cf, const double* Xi,
-                             double* Yi) {
-    const double* vb = reinterpret_cast<const double*>(B0->val);
-    const double* ve = reinterpret_cast<const double*>(E->val);
-#define HGM_SPMM_PERT_G(GV)                                                                                    \
-    {                                                                                                          \
-        const int64_t nb = (B0->rows + (BS / GV) - 1) / (BS / GV);                                             \
-        HGM_REQUIRE(nb <= 0x7fffffff, "spmm_pert: too many rows for one launch");                              \
-        launch(c, false, k_spmm_pert<NV, GV, SHARED>, dim3((unsigned)nb), dim3(BS), B0->rows, B0->rp, B0->ci,  \
-               vb, E->rp, E->ci, ve, cf, Xi, Yi);                                                              \
-    }
-    switch (B0->group) {
-        case 64: HGM_SPMM_PERT_G(64) break;
-        case 32: HGM_SPMM_PERT_G(32) break;
-        case 16: HGM_SPMM_PERT_G(16) break;
-        case 8: HGM_SPMM_PERT_G(8) break;
-        default: HGM_SPMM_PERT_G(4) break;
-    }
-#undef HGM_SPMM_PERT_G
-}
-
 void spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, bool shared, int nvec, const double* coefs,
                const double* Xi, double* Yi) {
     HGM_REQUIRE(B0->dtype == HGM_F64 && E->dtype == HGM_F64, "spmm_pert: fp64 operators only");
@@ -405,16 +356,16 @@ void spmm_pert(hgm_ctx* c, const hgm_mat* B0, const hgm_mat* E, bool shared, int
     if (B0->rows <= 0) return;
     PertCoef cf;
     for (int r = 0; r < SPMM_MAXV; ++r) cf.c[r] = r < nvec ? coefs[r] : 0.0;
-#define HGM_SPMM_PERT_NV(N)                                        \
-    if (shared) launch_spmm_pert<N, 1>(c, B0, E, cf, Xi, Yi);      \
-    else launch_spmm_pert<N, 0>(c, B0, E, cf, Xi, Yi);
-    switch (spmm_width(nvec)) {
-        case 1: HGM_SPMM_PERT_NV(1) break;
-        case 2: HGM_SPMM_PERT_NV(2) break;
-        case 4: HGM_SPMM_PERT_NV(4) break;
-        default: HGM_SPMM_PERT_NV(8) break;
-    }
-#undef HGM_SPMM_PERT_NV
+    const double* vb = reinterpret_cast<const double*>(B0->val);
+    const double* ve = reinterpret_cast<const double*>(E->val);
+    dispatch(
+        [&](auto nv, auto sh, auto g) {
+            const int64_t nb = (B0->rows + (BS / g) - 1) / (BS / g);
+            HGM_REQUIRE(nb <= 0x7fffffff, "spmm_pert: too many rows for one launch");
+            launch(c, false, k_spmm_pert<nv, g, sh>, dim3((unsigned)nb), dim3(BS), B0->rows, B0->rp, B0->ci, vb, E->rp,
+                   E->ci, ve, cf, Xi, Yi);
+        },
+        MvWidths{spmm_width(nvec)}, flag(shared), RowGroups{B0->group});
     HGM_HIP(hipGetLastError());
 }
 

@@ -29,7 +29,7 @@ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nb) {
 // NT: nontemporal (streaming) loads for val/col so they do not evict x from L2/MALL.
 // Per-lane partial of the dot product of entries [s, e) with x, lane gl of a G-lane group.
 #ifndef HGM_SPMV_U
-#define HGM_SPMV_U 4   // pairs per lane per iteration of the VEC row loop (C2 A: 4 beats 2 and 8)
+#define HGM_SPMV_U 4   // pairs per lane per iteration of the VEC row loop; at C2 A, 4 beats 2 and 8
 #endif
 // IX: column index type (int32_t, or uint16_t for the narrow copy ci16; scalar path only).
 template <typename T, int G, bool VEC, bool NT, typename IX = int32_t>
@@ -517,18 +517,23 @@ __global__ __launch_bounds__(BS) void k_spmv_seq(int64_t rows, const int64_t* __
     }
 }
 
+// The epilogues each site instantiates (dispatch.h; any other value takes the last entry).  The
+// streaming kernels have no EPI_DIVH: the band reduction or the row kernel applies it (spmv_pn_ok).
+using SeqEpis = Ints<EPI_NONE, EPI_ADD, EPI_SUB, EPI_RSUB>;
+using StreamEpis = Ints<EPI_NONE, EPI_ADD, EPI_SUB, EPI_ADDQ, EPI_RSUB>;
+using RowEpis = Ints<EPI_NONE, EPI_ADD, EPI_SUB, EPI_DIVH, EPI_ADDQ, EPI_RSUB>;   // row kernel, band reduction
+using NormEpis = Ints<EPI_SUB, EPI_RSUB>;         // row kernel with the fused sum of squares
+using PlainEpis = Ints<EPI_ADD, EPI_SUB, EPI_RSUB>;   // epilogue(), epilogue_to(): no fallback
+using Classes = Ints<KC_SPMV_B, KC_SPMV_A>;
+
 template <typename T>
 static void spmv_seq(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z) {
     HGM_REQUIRE(epi == EPI_NONE || epi == EPI_ADD || epi == EPI_SUB || epi == EPI_RSUB,
                 "parity mode: pending-normalisation epilogues are not used");
     const T* val = reinterpret_cast<const T*>(M->val);
     const dim3 g((unsigned)grid_for(M->rows)), b(BS);
-    switch (epi) {
-        case EPI_NONE: launch(c, true, k_spmv_seq<T, EPI_NONE>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z); break;
-        case EPI_ADD: launch(c, true, k_spmv_seq<T, EPI_ADD>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z); break;
-        case EPI_SUB: launch(c, true, k_spmv_seq<T, EPI_SUB>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z); break;
-        default: launch(c, true, k_spmv_seq<T, EPI_RSUB>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z); break;
-    }
+    dispatch([&](auto e) { launch(c, true, k_spmv_seq<T, e>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z); },
+             SeqEpis{epi});
 }
 
 int pick_group(int64_t rows, int64_t nnz) {
@@ -552,187 +557,109 @@ __global__ __launch_bounds__(BS) void k_epi(int64_t n, T* __restrict__ y, T a, c
 // launchers (every SpMV launch goes through hgm::launch so armed timing events ride
 // in the dispatch packets of the first / last kernel of the product)
 // ------------------------------------------------------------------------------
-template <typename T, int G, int EPI, bool NT, typename IX, int CLS>
-static void launch_stream_e(hgm_ctx* c, bool last, const SegIndex& si, const IX* ci, const T* val, const T* x,
-                            T* out, T a, const T* z, T* head, T* tail, const PendNorm<T>& pn, const Paged<T>& pg) {
-    if (si.nnz == 0) {
-        int64_t g = (si.nseg + BS - 1) / BS;
-        if (g > 4096) g = 4096;
-        if (g > 0) launch(c, last, k_fill_epi<T, EPI>, dim3(g), dim3(BS), si.nseg, out, a, z);
-        return;
-    }
-    if constexpr (std::is_same<IX, int32_t>::value) {
-        if (pg.pptr)
-            launch(c, false, k_spmv_stream<T, G, EPI, NT, IX, true, CLS>, dim3(si.nchunks), dim3(BS), si.nnz, si.nseg,
-                   si.sp, si.fo, ci, val, x, out, a, z, head, tail, pn, pg);
-        else
-            launch(c, false, k_spmv_stream<T, G, EPI, NT, IX, false, CLS>, dim3(si.nchunks), dim3(BS), si.nnz, si.nseg,
-                   si.sp, si.fo, ci, val, x, out, a, z, head, tail, pn, pg);
-    } else {
-        launch(c, false, k_spmv_stream<T, G, EPI, NT, IX, false, CLS>, dim3(si.nchunks), dim3(BS), si.nnz, si.nseg, si.sp,
-               si.fo, ci, val, x, out, a, z, head, tail, pn, pg);
-    }
-    int64_t g = (si.nchunks + BS - 1) / BS;
-    if (g > 4096) g = 4096;
-    launch(c, last, k_stream_fixup<T, EPI>, dim3(g), dim3(BS), si.nnz, si.nchunks, si.sp, si.fo, out, a, z,
-           (const T*)head, (const T*)tail, pn);
-}
-
-template <typename T, int G, bool NT, typename IX, int CLS>
-static void launch_stream_g(hgm_ctx* c, bool last, const SegIndex& si, const IX* ci, const T* val, const T* x,
-                            T* out, int epi, T a, const T* z, T* head, T* tail, const PendNorm<T>& pn,
-                            const Paged<T>& pg) {
-    switch (epi) {
-        case EPI_NONE: launch_stream_e<T, G, EPI_NONE, NT, IX, CLS>(c, last, si, ci, val, x, out, a, z, head, tail, pn, pg); break;
-        case EPI_ADD: launch_stream_e<T, G, EPI_ADD, NT, IX, CLS>(c, last, si, ci, val, x, out, a, z, head, tail, pn, pg); break;
-        case EPI_SUB: launch_stream_e<T, G, EPI_SUB, NT, IX, CLS>(c, last, si, ci, val, x, out, a, z, head, tail, pn, pg); break;
-        case EPI_ADDQ: launch_stream_e<T, G, EPI_ADDQ, NT, IX, CLS>(c, last, si, ci, val, x, out, a, z, head, tail, pn, pg); break;
-        default: launch_stream_e<T, G, EPI_RSUB, NT, IX, CLS>(c, last, si, ci, val, x, out, a, z, head, tail, pn, pg); break;
-    }
-}
-
 template <typename T, typename IX = int32_t>
 static void spmv_stream(hgm_ctx* c, bool last, const SegIndex& si, int G, bool nt, const IX* ci, const T* val,
                         const T* x, T* out, int epi, T a, const T* z, const PendNorm<T>& pn = PendNorm<T>{},
                         const Paged<T>& pg = Paged<T>{}, int kclass = KC_SPMV_A) {
     T* head = c->buf<T>("stream_head", si.nchunks + 1);
     T* tail = c->buf<T>("stream_tail", si.nchunks + 1);
-#define HGM_SG(GG)                                                                                          \
-    if (kclass == KC_SPMV_B) {                                                                              \
-        if (nt) launch_stream_g<T, GG, true, IX, KC_SPMV_B>(c, last, si, ci, val, x, out, epi, a, z, head, tail, pn, pg); \
-        else launch_stream_g<T, GG, false, IX, KC_SPMV_B>(c, last, si, ci, val, x, out, epi, a, z, head, tail, pn, pg); \
-    } else {                                                                                                \
-        if (nt) launch_stream_g<T, GG, true, IX, KC_SPMV_A>(c, last, si, ci, val, x, out, epi, a, z, head, tail, pn, pg); \
-        else launch_stream_g<T, GG, false, IX, KC_SPMV_A>(c, last, si, ci, val, x, out, epi, a, z, head, tail, pn, pg); \
-    }
-    switch (G) {
-        case 64: HGM_SG(64) break;
-        case 32: HGM_SG(32) break;
-        case 16: HGM_SG(16) break;
-        case 8: HGM_SG(8) break;
-        case 2: HGM_SG(2) break;
-        default: HGM_SG(4) break;
-    }
-#undef HGM_SG
-}
-
-template <typename T, int G, bool VEC, bool NT, typename IX = int32_t>
-static void launch_spmv_v(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z,
-                          const PendNorm<T>& pn) {
-    const int64_t nb = (M->rows + (BS / G) - 1) / (BS / G);
-    if (nb == 0) return;
-    const T* val = reinterpret_cast<const T*>(M->val);
-    const IX* ci = sizeof(IX) == 2 ? reinterpret_cast<const IX*>(M->ci16) : reinterpret_cast<const IX*>(M->ci);
-    const int xcd = (M->variant & SPMV_XCD) ? 1 : 0;
-    const dim3 g((unsigned)nb), b(BS);
-    T* np_ = nullptr;
-    switch (epi) {
-        case EPI_NONE: launch(c, true, k_spmv<T, G, EPI_NONE, VEC, NT, false, IX>, g, b, M->rows, M->rp, ci, val, x, y, a, z, xcd, np_, pn); break;
-        case EPI_ADD: launch(c, true, k_spmv<T, G, EPI_ADD, VEC, NT, false, IX>, g, b, M->rows, M->rp, ci, val, x, y, a, z, xcd, np_, pn); break;
-        case EPI_SUB: launch(c, true, k_spmv<T, G, EPI_SUB, VEC, NT, false, IX>, g, b, M->rows, M->rp, ci, val, x, y, a, z, xcd, np_, pn); break;
-        case EPI_DIVH: launch(c, true, k_spmv<T, G, EPI_DIVH, VEC, NT, false, IX>, g, b, M->rows, M->rp, ci, val, x, y, a, z, xcd, np_, pn); break;
-        case EPI_ADDQ: launch(c, true, k_spmv<T, G, EPI_ADDQ, VEC, NT, false, IX>, g, b, M->rows, M->rp, ci, val, x, y, a, z, xcd, np_, pn); break;
-        default: launch(c, true, k_spmv<T, G, EPI_RSUB, VEC, NT, false, IX>, g, b, M->rows, M->rp, ci, val, x, y, a, z, xcd, np_, pn); break;
-    }
-}
-
-// row kernel with the fused sum of squares of the output (EPI_SUB / EPI_RSUB)
-template <typename T, int G, bool VEC, bool NT>
-static void launch_spmv_nrm_v(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z, T* out) {
-    const int64_t nb = (M->rows + (BS / G) - 1) / (BS / G);
-    if (nb == 0) {
-        HGM_HIP(hipMemsetAsync(out, 0, sizeof(T), c->stream));
+    if (si.nnz == 0) {
+        int64_t g = (si.nseg + BS - 1) / BS;
+        if (g > 4096) g = 4096;
+        if (g > 0)
+            dispatch([&](auto e) { launch(c, last, k_fill_epi<T, e>, dim3(g), dim3(BS), si.nseg, out, a, z); },
+                     StreamEpis{epi});
         return;
     }
-    const T* val = reinterpret_cast<const T*>(M->val);
-    const int xcd = (M->variant & SPMV_XCD) ? 1 : 0;
-    T* parts = c->buf<T>("spmv_nparts", nb + 1);
-    const dim3 g((unsigned)nb), b(BS);
-    if (epi == EPI_SUB)
-        launch(c, true, k_spmv<T, G, EPI_SUB, VEC, NT, true>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z, xcd, parts,
-               PendNorm<T>{});
-    else
-        launch(c, true, k_spmv<T, G, EPI_RSUB, VEC, NT, true>, g, b, M->rows, M->rp, M->ci, val, x, y, a, z, xcd, parts,
-               PendNorm<T>{});
-    hipLaunchKernelGGL(k_sum_parts<T>, dim3(1), dim3(BS), 0, c->stream, (const T*)parts, nb, out);
+    constexpr bool WIDE = std::is_same<IX, int32_t>::value;   // a uint16 index stream has no paged kernel
+    dispatch(
+        [&](auto g, auto ntv, auto cls, auto e, auto paged) {
+            constexpr bool NT = ntv, PG = paged;
+            if constexpr (WIDE || !PG)
+                launch(c, false, k_spmv_stream<T, g, e, NT, IX, PG, cls>, dim3(si.nchunks), dim3(BS), si.nnz, si.nseg,
+                       si.sp, si.fo, ci, val, x, out, a, z, head, tail, pn, pg);
+            int64_t fg = (si.nchunks + BS - 1) / BS;
+            if (fg > 4096) fg = 4096;
+            launch(c, last, k_stream_fixup<T, e>, dim3(fg), dim3(BS), si.nnz, si.nchunks, si.sp, si.fo, out, a, z,
+                   (const T*)head, (const T*)tail, pn);
+        },
+        StreamGroups{G}, flag(nt), Classes{kclass}, StreamEpis{epi}, flag(WIDE && pg.pptr));
 }
 
-template <typename T, int G>
-static void launch_spmv_g(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z, T* nrm,
-                          const PendNorm<T>& pn) {
+// one G-lane group per row; nrm: also the sum of squares of the output (EPI_SUB / EPI_RSUB)
+template <typename T>
+static void spmv_rows(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z, T* nrm,
+                      const PendNorm<T>& pn) {
     const bool vec = M->variant & SPMV_VEC, nt = M->variant & SPMV_NT;
+    const T* val = reinterpret_cast<const T*>(M->val);
+    const int xcd = (M->variant & SPMV_XCD) ? 1 : 0;
     if (nrm) {
-        if (vec && nt) launch_spmv_nrm_v<T, G, true, true>(c, M, x, y, epi, a, z, nrm);
-        else if (vec) launch_spmv_nrm_v<T, G, true, false>(c, M, x, y, epi, a, z, nrm);
-        else if (nt) launch_spmv_nrm_v<T, G, false, true>(c, M, x, y, epi, a, z, nrm);
-        else launch_spmv_nrm_v<T, G, false, false>(c, M, x, y, epi, a, z, nrm);
+        dispatch(
+            [&](auto g, auto v, auto ntv, auto e) {
+                constexpr bool VEC = v, NT = ntv;
+                const int64_t nb = (M->rows + (BS / g) - 1) / (BS / g);
+                if (nb == 0) {
+                    HGM_HIP(hipMemsetAsync(nrm, 0, sizeof(T), c->stream));
+                    return;
+                }
+                T* parts = c->buf<T>("spmv_nparts", nb + 1);
+                launch(c, true, k_spmv<T, g, e, VEC, NT, true>, dim3((unsigned)nb), dim3(BS), M->rows, M->rp, M->ci,
+                       val, x, y, a, z, xcd, parts, PendNorm<T>{});
+                hipLaunchKernelGGL(k_sum_parts<T>, dim3(1), dim3(BS), 0, c->stream, (const T*)parts, nb, nrm);
+            },
+            RowGroups{M->group}, flag(vec), flag(nt), NormEpis{epi});
         return;
     }
-    if (vec && nt) launch_spmv_v<T, G, true, true>(c, M, x, y, epi, a, z, pn);
-    else if (vec) launch_spmv_v<T, G, true, false>(c, M, x, y, epi, a, z, pn);
-    else if (M->ci16 && nt) launch_spmv_v<T, G, false, true, uint16_t>(c, M, x, y, epi, a, z, pn);
-    else if (M->ci16) launch_spmv_v<T, G, false, false, uint16_t>(c, M, x, y, epi, a, z, pn);
-    else if (nt) launch_spmv_v<T, G, false, true>(c, M, x, y, epi, a, z, pn);
-    else launch_spmv_v<T, G, false, false>(c, M, x, y, epi, a, z, pn);
-}
-
-template <typename T, int G, bool VEC, bool NT>
-static void launch_band_v(hgm_ctx* c, const hgm_mat* M, const T* x, T* yp) {
-    constexpr int RPB = BS / G;
-    const int64_t items = (M->rows + RPB - 1) / RPB * M->nbands;
-    int64_t grid = 256 * 8;                      // ~all resident blocks, grid-stride in band-major order
-    if (grid > items) grid = items;
-    if (grid < 1) return;
-    launch(c, false, k_spmv_band<T, G, VEC, NT>, dim3((unsigned)grid), dim3(BS), M->rows, M->nbands, M->brp, M->bci,
-           reinterpret_cast<const T*>(M->bval), x, yp);
-}
-
-template <typename T, int G>
-static void launch_band_g(hgm_ctx* c, const hgm_mat* M, const T* x, T* yp) {
-    const bool vec = M->variant & SPMV_VEC, nt = M->variant & SPMV_NT;
-    if (vec && nt) launch_band_v<T, G, true, true>(c, M, x, yp);
-    else if (vec) launch_band_v<T, G, true, false>(c, M, x, yp);
-    else if (nt) launch_band_v<T, G, false, true>(c, M, x, yp);
-    else launch_band_v<T, G, false, false>(c, M, x, yp);
-}
-
-template <typename T, int EPI>
-static void launch_band_reduce(hgm_ctx* c, const hgm_mat* M, const T* yp, T* y, T a, const T* z,
-                               const PendNorm<T>& pn) {
-    launch(c, true, k_band_reduce<T, EPI>, dim3(grid_for(M->rows)), dim3(BS), M->rows, M->nbands, yp, y, a, z, pn);
+    // the 16-bit copy of the column indices serves the scalar loads only (seg_partial)
+    dispatch(
+        [&](auto g, auto v, auto ntv, auto narrow, auto e) {
+            constexpr bool VEC = v, NT = ntv, N16 = narrow;
+            if constexpr (!(VEC && N16)) {
+                using IX = std::conditional_t<N16, uint16_t, int32_t>;
+                const int64_t nb = (M->rows + (BS / g) - 1) / (BS / g);
+                if (nb == 0) return;
+                const IX* ci = N16 ? reinterpret_cast<const IX*>(M->ci16) : reinterpret_cast<const IX*>(M->ci);
+                T* np_ = nullptr;
+                launch(c, true, k_spmv<T, g, e, VEC, NT, false, IX>, dim3((unsigned)nb), dim3(BS), M->rows, M->rp, ci,
+                       val, x, y, a, z, xcd, np_, pn);
+            }
+        },
+        RowGroups{M->group}, flag(vec), flag(nt), flag(!vec && M->ci16), RowEpis{epi});
 }
 
 template <typename T>
 static void band_reduce(hgm_ctx* c, const hgm_mat* M, const T* yp, T* y, int epi, T a, const T* z,
                         const PendNorm<T>& pn) {
-    switch (epi) {
-        case EPI_NONE: launch_band_reduce<T, EPI_NONE>(c, M, yp, y, a, z, pn); break;
-        case EPI_ADD: launch_band_reduce<T, EPI_ADD>(c, M, yp, y, a, z, pn); break;
-        case EPI_SUB: launch_band_reduce<T, EPI_SUB>(c, M, yp, y, a, z, pn); break;
-        case EPI_DIVH: launch_band_reduce<T, EPI_DIVH>(c, M, yp, y, a, z, pn); break;
-        case EPI_ADDQ: launch_band_reduce<T, EPI_ADDQ>(c, M, yp, y, a, z, pn); break;
-        default: launch_band_reduce<T, EPI_RSUB>(c, M, yp, y, a, z, pn); break;
-    }
+    dispatch(
+        [&](auto e) {
+            launch(c, true, k_band_reduce<T, e>, dim3(grid_for(M->rows)), dim3(BS), M->rows, M->nbands, yp, y, a, z,
+                   pn);
+        },
+        RowEpis{epi});
 }
 
 template <typename T>
 static void spmv_banded(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z,
                         const PendNorm<T>& pn) {
     T* yp = c->buf<T>("band_part", (size_t)M->nbands * M->rows + 1);
-    switch (M->bgroup) {
-        case 64: launch_band_g<T, 64>(c, M, x, yp); break;
-        case 32: launch_band_g<T, 32>(c, M, x, yp); break;
-        case 16: launch_band_g<T, 16>(c, M, x, yp); break;
-        case 8: launch_band_g<T, 8>(c, M, x, yp); break;
-        default: launch_band_g<T, 4>(c, M, x, yp); break;
-    }
+    dispatch(
+        [&](auto g, auto v, auto ntv) {
+            constexpr bool VEC = v, NT = ntv;
+            constexpr int RPB = BS / g;
+            const int64_t items = (M->rows + RPB - 1) / RPB * M->nbands;
+            int64_t grid = 256 * 8;                      // ~all resident blocks, grid-stride in band-major order
+            if (grid > items) grid = items;
+            if (grid < 1) return;
+            launch(c, false, k_spmv_band<T, g, VEC, NT>, dim3((unsigned)grid), dim3(BS), M->rows, M->nbands, M->brp,
+                   M->bci, reinterpret_cast<const T*>(M->bval), x, yp);
+        },
+        BandGroups{M->bgroup}, flag(M->variant & SPMV_VEC), flag(M->variant & SPMV_NT));
     band_reduce<T>(c, M, yp, y, epi, a, z, pn);
 }
 
 template <typename T>
 static void spmv_streamed(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T* z,
                           const PendNorm<T>& pn, int kclass) {
-    const int kc = kclass == KC_SPMV_B ? KC_SPMV_B : KC_SPMV_A;
     const bool nt = M->variant & SPMV_NT;
     // paged x gathers need the page index and a 16-B aligned x (vector page loads)
     Paged<T> pg;
@@ -747,7 +674,7 @@ static void spmv_streamed(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int ep
         T* yp = c->buf<T>("band_part", (size_t)M->nbands * M->rows + 1);
         SegIndex si{M->nnz, (int64_t)M->nbands * M->rows, stream_chunks(M->nnz), M->brp, M->bcfo};
         spmv_stream<T>(c, false, si, M->bsgroup, nt, M->bci, reinterpret_cast<const T*>(M->bval), x, yp, EPI_NONE,
-                       T(0), nullptr, PendNorm<T>{}, pg, kc);
+                       T(0), nullptr, PendNorm<T>{}, pg, kclass);
         band_reduce<T>(c, M, yp, y, epi, a, z, pn);
     } else {
         SegIndex si{M->nnz, M->rows, stream_chunks(M->nnz), M->rp, M->cfo};
@@ -755,17 +682,21 @@ static void spmv_streamed(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int ep
         // 16-bit page-local indices instead, and only chunks past the page limit read M->ci
         if (M->ci16 && !(pg.pptr && c->num.paged16))
             spmv_stream<T, uint16_t>(c, true, si, M->sgroup, nt, M->ci16, reinterpret_cast<const T*>(M->val), x, y,
-                                     epi, a, z, pn, pg, kc);
+                                     epi, a, z, pn, pg, kclass);
         else
             spmv_stream<T>(c, true, si, M->sgroup, nt, M->ci, reinterpret_cast<const T*>(M->val), x, y, epi, a, z, pn,
-                           pg, kc);
+                           pg, kclass);
     }
+}
+
+// whether the nnz-balanced streaming kernel serves this operator (its chunk index exists)
+static bool spmv_streams(const hgm_mat* M) {
+    return (M->variant & SPMV_STREAM) && (M->nbands > 1 ? M->bcfo != nullptr : M->cfo != nullptr);
 }
 
 bool spmv_pn_ok(const hgm_mat* M, int epi) {
     if (M->nnz == 0) return false;
-    const bool stream = (M->variant & SPMV_STREAM) && (M->nbands > 1 ? M->bcfo != nullptr : M->cfo != nullptr);
-    if (epi == EPI_DIVH) return !(stream && M->nbands <= 1);   // row kernel or band reduction
+    if (epi == EPI_DIVH) return !(spmv_streams(M) && M->nbands <= 1);   // row kernel or band reduction
     return epi == EPI_ADDQ;
 }
 
@@ -776,24 +707,13 @@ void spmv(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T*
     HGM_REQUIRE((epi != EPI_DIVH && epi != EPI_ADDQ) || (pnp && spmv_pn_ok(M, epi)), "spmv: pending-norm epilogue");
     hipEvent_t t0 = nullptr;
     timing_begin(c, kclass, &t0);
-    const bool stream = (M->variant & SPMV_STREAM) && (M->nbands > 1 ? M->bcfo != nullptr : M->cfo != nullptr);
+    const bool stream = spmv_streams(M);
     const bool rowk = !stream && M->nbands <= 1;
     T* nrm = (rowk && !c->num.parity && (epi == EPI_SUB || epi == EPI_RSUB)) ? sumsq_out : nullptr;
-    if (c->num.parity) {
-        spmv_seq<T>(c, M, x, y, epi, a, z);
-    } else if (stream) {
-        spmv_streamed<T>(c, M, x, y, epi, a, z, pn, kclass);
-    } else if (M->nbands > 1) {
-        spmv_banded<T>(c, M, x, y, epi, a, z, pn);
-    } else {
-        switch (M->group) {
-            case 64: launch_spmv_g<T, 64>(c, M, x, y, epi, a, z, nrm, pn); break;
-            case 32: launch_spmv_g<T, 32>(c, M, x, y, epi, a, z, nrm, pn); break;
-            case 16: launch_spmv_g<T, 16>(c, M, x, y, epi, a, z, nrm, pn); break;
-            case 8: launch_spmv_g<T, 8>(c, M, x, y, epi, a, z, nrm, pn); break;
-            default: launch_spmv_g<T, 4>(c, M, x, y, epi, a, z, nrm, pn); break;
-        }
-    }
+    if (c->num.parity) spmv_seq<T>(c, M, x, y, epi, a, z);
+    else if (stream) spmv_streamed<T>(c, M, x, y, epi, a, z, pn, kclass);
+    else if (M->nbands > 1) spmv_banded<T>(c, M, x, y, epi, a, z, pn);
+    else spmv_rows<T>(c, M, x, y, epi, a, z, nrm, pn);
     // other kernels: separate fixed-order reduction of the output
     if (sumsq_out && !nrm) sumsq<T>(c, M->rows, y, sumsq_out);
     HGM_HIP(hipGetLastError());
@@ -812,12 +732,7 @@ void spmv(hgm_ctx* c, const hgm_mat* M, const T* x, T* y, int epi, T a, const T*
 template <typename T>
 void epilogue(hgm_ctx* c, int64_t n, T* y, int epi, T a, const T* z) {
     const int g = grid_for(n);
-    switch (epi) {
-        case EPI_ADD: k_epi<T, EPI_ADD><<<g, BS, 0, c->stream>>>(n, y, a, z); break;
-        case EPI_SUB: k_epi<T, EPI_SUB><<<g, BS, 0, c->stream>>>(n, y, a, z); break;
-        case EPI_RSUB: k_epi<T, EPI_RSUB><<<g, BS, 0, c->stream>>>(n, y, a, z); break;
-        default: return;
-    }
+    if (!dispatch([&](auto e) { k_epi<T, e><<<g, BS, 0, c->stream>>>(n, y, a, z); }, PlainEpis{epi, false})) return;
     HGM_HIP(hipGetLastError());
 }
 
@@ -830,13 +745,9 @@ __global__ __launch_bounds__(BS) void k_epi_to(int64_t n, const T* __restrict__ 
 template <typename T>
 void epilogue_to(hgm_ctx* c, int64_t n, const T* in, T* out, int epi, T a, const T* z) {
     const int g = grid_for(n);
-    switch (epi) {
-        case EPI_ADD: k_epi_to<T, EPI_ADD><<<g, BS, 0, c->stream>>>(n, in, out, a, z); break;
-        case EPI_SUB: k_epi_to<T, EPI_SUB><<<g, BS, 0, c->stream>>>(n, in, out, a, z); break;
-        case EPI_RSUB: k_epi_to<T, EPI_RSUB><<<g, BS, 0, c->stream>>>(n, in, out, a, z); break;
-        default:
-            if (in != out) HGM_HIP(hipMemcpyAsync(out, in, sizeof(T) * n, hipMemcpyDeviceToDevice, c->stream));
-            return;
+    if (!dispatch([&](auto e) { k_epi_to<T, e><<<g, BS, 0, c->stream>>>(n, in, out, a, z); }, PlainEpis{epi, false})) {
+        if (in != out) HGM_HIP(hipMemcpyAsync(out, in, sizeof(T) * n, hipMemcpyDeviceToDevice, c->stream));
+        return;
     }
     HGM_HIP(hipGetLastError());
 }

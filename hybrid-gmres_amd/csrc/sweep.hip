@@ -171,15 +171,11 @@ void proj_norms(hgm_ctx* c, int64_t rows, int k, const T* V, int64_t ldv, const 
     double* parts = c->buf<double>("pn_parts", (size_t)2 * L * nb);
     const size_t lds = sizeof(double) * (size_t)lc * pn_lds_stride(k);
     const dim3 grid((unsigned)nb, (unsigned)nchunks);
-    auto go = [&](auto kern) {
-        kern<<<grid, BS, lds, c->stream>>>(rows, k, V, ldv, Y, ldy, L, lc, t, parts);
-    };
-    if (k <= 4) go(k_proj_norms<1>);
-    else if (k <= 8) go(k_proj_norms<2>);
-    else if (k <= 16) go(k_proj_norms<4>);
-    else if (k <= 32) go(k_proj_norms<8>);
-    else if (k <= 64) go(k_proj_norms<16>);
-    else go(k_proj_norms<0>);
+    // KQ of the kernel: the smallest instantiated register count with k <= 4 KQ, else 0 (operands re-read)
+    using ProjSteps = Ints<1, 2, 4, 8, 16, 0>;
+    const int kq = k <= 4 ? 1 : k <= 8 ? 2 : k <= 16 ? 4 : k <= 32 ? 8 : k <= 64 ? 16 : 0;
+    dispatch([&](auto kqv) { k_proj_norms<kqv><<<grid, BS, lds, c->stream>>>(rows, k, V, ldv, Y, ldy, L, lc, t, parts); },
+             ProjSteps{kq});
     k_pn_finalize<<<s_out ? 2 * L : L, BS, 0, c->stream>>>(parts, (int)nb, L, d_out, s_out);
     HGM_HIP(hipGetLastError());
 }
