@@ -683,8 +683,17 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
     constexpr int CH = 64 * EPL;                 // entries per chunk
     constexpr int ES = (int)sizeof(T);
     constexpr int AS = (int)(sizeof(TA) / sizeof(T));   // accumulator offset = slot offset * AS
-    __shared__ T qloc[MAXR];                     // (the last 64: the lanes' dummy slots)
-    __shared__ TA acc[W][NA][MAXR];
+    // One shared object, q first: two __shared__ arrays are laid out by size, the accumulators
+    // at offset 0 and q behind them, past the 16-bit offset field of the DS instructions, and
+    // every q, table and dummy access then pays a VALU add of q's base.  With q at 0 those are
+    // immediates on the slot registers.
+    struct Lds {
+        T q[MAXR];                               // (the last 64: the lanes' dummy slots)
+        TA acc[W][NA][MAXR];
+    };
+    __shared__ Lds lds;
+    T(&qloc)[MAXR] = lds.q;
+    TA(&acc)[W][NA][MAXR] = lds.acc;
     const int g = blockIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int ln = threadIdx.x & 63;
@@ -853,26 +862,28 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
             const uint32_t dlo = (uint32_t)rpv, dhi = (uint32_t)((uint64_t)rpv >> 32);
             const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)dlo, 0);
             const uint32_t pN = (uint32_t)__builtin_amdgcn_readlane((int)dlo, G / 2);
+            // A unit past the batch's last needs no select of its own: the clamped descriptor load
+            // gives it the batch's end twice (no value pairs: every lane's offset is past every
+            // range, zeros), its slot words' lane offsets lie past the slot range (zeros: the unit
+            // goes into the lane offset, four loop-invariant registers, because the range check is
+            // sure to see that one), and off = 0 sends every lane to its dummy slot whatever len
+            // holds.
             const __amdgpu_buffer_rsrc_t rv = buf_rsrc(val + 2 * (int64_t)p0, (int)((pN - p0) * 16u));
             const __amdgpu_buffer_rsrc_t rl = buf_rsrc(lidx + 128 * (int64_t)un, nu * 256);
 #pragma unroll
             for (int u = 0; u < G / 2; ++u) {
-                const bool live = u < nu;
                 const uint32_t pa = (uint32_t)__builtin_amdgcn_readlane((int)dlo, u);
                 const uint32_t pb = (uint32_t)__builtin_amdgcn_readlane((int)dlo, u + 1);
                 const uint32_t cw = (uint32_t)__builtin_amdgcn_readlane((int)dhi, u);
-                b.len[2 * u] = live ? (int)(cw & 0xffu) : 0;
+                b.len[2 * u] = (int)(cw & 0xffu);
                 b.len[2 * u + 1] = 0;
-                b.off[2 * u] = live ? 1 : 0;
-                const int c0h = live ? (int)((cw >> 8) & 0xffu) : 0;
-                const int np = live ? (int)(pb - pa) : 0;      // the unit's value pairs
-                const int t = ln - c0h;
-                const int vo = (uint32_t)t < (uint32_t)np ? t * 16 : (1 << 30);
-                const int lo = live ? ln * 4 : (1 << 30);
+                b.off[2 * u] = u < nu ? 1 : 0;
+                const int t = ln - (int)((cw >> 8) & 0xffu);
+                const int vo = (uint32_t)t < pb - pa ? t * 16 : (1 << 30);   // (the unit's value pairs)
                 const double2 tv = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rv, vo, (int)((pa - p0) * 16u), HGM_RW_AUX));
                 b.v[u][0][0] = (T)tv.x;
                 b.v[u][0][EPL - 1] = (T)tv.y;
-                b.s[u][0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rl, lo, u * 256, HGM_RW_AUX);
+                b.s[u][0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rl, ln * 4 + u * 256, 0, HGM_RW_AUX);
             }
             return;
         }
@@ -1062,14 +1073,19 @@ __global__ __launch_bounds__(64 * W) void k_fused_rw(const int64_t* __restrict__
 #pragma unroll
                 for (int e = 0; e < EPL; ++e)
                     tb[u][e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + VTAB * ES + c8[u][e]);
+            // (the table reads first, then the units' q reads in unit order: the counted waits of
+            // phase 3 rely on it, and with every read an immediate offset from q at LDS address 0
+            // the scheduler otherwise mixes the 24 and the waits become 14, 6, 3, 0)
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int u = 0; u < G / 2; ++u)
+            for (int u = 0; u < G / 2; ++u) {
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) {
                     qa[u][e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + k[u][0][e]);
                     qb[u][e] = *reinterpret_cast<const T*>(reinterpret_cast<const char*>(qloc) + kb[u][e]);
                 }
-            __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int u = 0; u < G / 2; ++u) {
                 asm volatile("" : "+v"(tb[u][0]), "+v"(tb[u][EPL - 1]));
