@@ -157,7 +157,7 @@ def test_spmv_empty_rows_and_ragged(gpu_ctx):
 
 
 def _ragged_matrix():
-    """Rows longer than several 2048-entry chunks, empty rows (leading, inner,
+    """Rows longer than one and two 4096-entry chunks, empty rows (leading, inner,
     trailing), a single-entry row and short rows."""
     rng = np.random.default_rng(5)
     n = 7000
