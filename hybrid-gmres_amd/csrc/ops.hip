@@ -30,6 +30,13 @@ hgm_mat* mat_alloc(hgm_ctx* c, int64_t rows, int64_t cols, int64_t nnz, int dtyp
         mat_free(M);
         throw Error{HGM_E_NOMEM, "hipMalloc failed for sparse matrix"};
     }
+    // The values past nnz are zeros, not what the allocation held: the one pass's pair load at the end of
+    // the last row takes val[nnz] too and multiplies it by the q = 0 of a dummy slot, and NaN * 0 is NaN
+    // (every fill of val runs on c->stream or after it, and none writes past nnz).
+    if (hipMemsetAsync((char*)M->val + vs * nnz, 0, vs * 4, c->stream) != hipSuccess) {
+        mat_free(M);
+        throw Error{HGM_E_HIP, "hipMemset failed for sparse matrix"};
+    }
     M->group = pick_group(rows, nnz);
     M->variant = SPMV_VEC;
     return M;
