@@ -384,7 +384,7 @@ extern "C" {
 
 HGM_API int hgm_version(void) { return HGM_VERSION; }
 
-HGM_API int hgm_experiments(void) { return HGM_EXPERIMENTS; }
+HGM_API int hgm_experiments(void) { return 0; }
 
 HGM_API int hgm_runtime_check(char* msg, int len) {
     const std::set<std::string> names = hip_runtimes();
@@ -488,6 +488,28 @@ HGM_API void hgm_ctx_destroy(hgm_ctx* c) {
 
 HGM_API const char* hgm_last_error(const hgm_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
+// Options that selected measured variants of the one-pass kernel, since retired (DESIGN.md §3.5
+// records each measurement).  The numbers stay: such an option takes and returns its production
+// value alone.  Options 32, 34 and 38 keep their production values and refuse the retired ones.
+static const char* const kRetiredMsg =
+    "a retired variant of the one-pass kernel (it lived in the experiments build; measurements: DESIGN.md §3.5): "
+    "only the production value is accepted";
+static bool retired_option(int option, double* production) {
+    switch (option) {
+        case HGM_OPT_FUSED_REGION: *production = 64; return true;
+        case HGM_OPT_FUSED_BS: *production = 1024; return true;
+        case HGM_OPT_FUSED_DBG: *production = 0; return true;
+        case HGM_OPT_FUSED_PF: *production = 2; return true;
+        case HGM_OPT_FUSED_KIND: *production = 1; return true;
+        case HGM_OPT_FUSED_WAVES: *production = 4; return true;
+        case HGM_OPT_FUSED_GROUP: *production = 8; return true;
+        case HGM_OPT_FUSED_DEPTH: *production = 2; return true;
+        case HGM_OPT_FUSED_PAIRS: *production = 1; return true;
+        case HGM_OPT_FUSED_ACC32: *production = 1; return true;
+        default: return false;
+    }
+}
+
 HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
     if (!c) return HGM_E_ARG;
     hgm::Numerics& n = c->num;
@@ -496,27 +518,8 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
         c->err = std::string("hgm_ctx_set_option: ") + what;
         return HGM_E_ARG;
     };
-    if (!HGM_EXPERIMENTS) {
-        // measured variants of the one-pass kernel: compiled into the experiments build only
-        bool variant = false;
-        switch (option) {
-            case HGM_OPT_FUSED_REGION: variant = v != 64; break;
-            case HGM_OPT_FUSED_BS: variant = v != 1024; break;
-            case HGM_OPT_FUSED_DBG: variant = v != 0; break;
-            case HGM_OPT_FUSED_PF: variant = v != 2; break;
-            case HGM_OPT_FUSED_KIND: variant = v != 1; break;
-            case HGM_OPT_FUSED_WAVES: variant = v != 4; break;
-            case HGM_OPT_FUSED_GROUP: variant = v != 8; break;
-            case HGM_OPT_FUSED_DEPTH: variant = v != 2; break;
-            case HGM_OPT_FUSED_PAIRS: variant = v != 1; break;
-            case HGM_OPT_FUSED_ACC32: variant = v != 1; break;
-            case HGM_OPT_FUSED_REDUCE: variant = !(v == 0 || v == 1); break;
-            case HGM_OPT_FUSED_ROWPAIR: variant = !(v == 0 || v == 4); break;
-            case HGM_OPT_FUSED_VSDEPTH: variant = (v == 2 || v == 3 || v == 4) && !(v == 2 || v == HGM_VSDEPTH_DEFAULT); break;
-            default: break;
-        }
-        if (variant) return bad("a measured variant of the one-pass kernel: experiments build only (HGM_EXPERIMENTS=1)");
-    }
+    double production = 0;
+    if (retired_option(option, &production)) return v == production ? HGM_OK : bad(kRetiredMsg);
     switch (option) {
         case HGM_OPT_PARITY: if (!b01) return bad("parity is 0 or 1"); n.parity = v != 0; break;
         case HGM_OPT_MGS_FORM: if (!b01) return bad("mgs form is 0 or 1"); n.mgs_form = (int)v; break;
@@ -551,49 +554,18 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
         case HGM_OPT_PAGED16: n.paged16 = v != 0.0; break;
         case HGM_OPT_BAND_DUAL: n.band_dual = v != 0.0; break;
         case HGM_OPT_FUSED_AB: if (!b01) return bad("fused_ab is 0 or 1"); n.fused_ab = v != 0; break;
-        case HGM_OPT_FUSED_REGION:
-            if (!(v >= 8 && v <= 1024 && v == std::floor(v))) return bad("fused_region is an integer in [8, 1024]");
-            n.fused_region = (int)v;
-            break;
-        case HGM_OPT_FUSED_BS:
-            if (!(v == 512 || v == 1024)) return bad("fused_bs is 512 or 1024");
-            n.fused_bs = (int)v;
-            break;
-        case HGM_OPT_FUSED_PF: if (v < 0 || v > 4) return bad("fused_pf is 0..4"); n.fused_pf = v < 1 ? 1 : (int)v; break;
         case HGM_OPT_KRYLOV_PAD: if (v < -1 || v > 65536 || v != (double)(int64_t)v || (v > 0 && (int64_t)v % 64)) return bad("krylov_pad is -1 or a multiple of 64 in 0..65536"); n.krylov_pad = (int)v; break;
-        case HGM_OPT_FUSED_DBG:
-            if (!(v >= 0 && v <= 15 && v == std::floor(v))) return bad("fused_dbg is 0..15");
-            n.fused_dbg = (int)v;
-            break;
-        case HGM_OPT_FUSED_KIND: if (!b01) return bad("fused_kind is 0 or 1"); n.fused_kind = (int)v; break;
         case HGM_OPT_FUSED_WREGION:
             if (!(v >= 4 && v <= 256 && v == std::floor(v))) return bad("fused_wregion is an integer in [4, 256]");
             n.fused_wregion = (int)v;
             break;
-        case HGM_OPT_FUSED_WAVES:
-            if (!(v == 1 || v == 2 || v == 4)) return bad("fused_waves is 1, 2 or 4");
-            n.fused_waves = (int)v;
-            break;
-        case HGM_OPT_FUSED_GROUP:
-            if (!(v == 4 || v == 8)) return bad("fused_group is 4 or 8");
-            n.fused_group = (int)v;
-            break;
-        case HGM_OPT_FUSED_DEPTH:
-            if (!(v == 2 || v == 3 || v == 4)) return bad("fused_depth is 2, 3 or 4");
-            n.fused_depth = (int)v;
-            break;
-        case HGM_OPT_FUSED_PAIRS: if (!b01) return bad("fused_pairs is 0 or 1"); n.fused_pairs = v != 0; break;
-        case HGM_OPT_FUSED_ACC32:
-            if (!(v == 0 || v == 1 || v == 2)) return bad("fused_acc32 is 0, 1 or 2");
-            n.fused_acc32 = (int)v;
-            break;
         case HGM_OPT_FUSED_PLAN_DEV: if (!b01) return bad("fused_plan_dev is 0 or 1"); n.fused_plan_dev = v != 0; break;
         case HGM_OPT_FUSED_REDUCE:
-            if (!(v == 0 || v == 1 || v == 2 || v == 3 || v == 4)) return bad("fused_reduce is 0 to 4");
+            if (!(v == 0 || v == 1)) return bad(kRetiredMsg);
             n.fused_reduce = (int)v;
             break;
         case HGM_OPT_FUSED_ROWPAIR:
-            if (!(v == 0 || v == 1 || v == 2 || v == 3 || v == 4)) return bad("fused_rowpair is 0 to 4");
+            if (!(v == 0 || v == 4)) return bad(kRetiredMsg);
             n.fused_rowpair = (int)v;
             break;
         case HGM_OPT_FUSED_VSTREAM:
@@ -601,7 +573,8 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
             n.fused_vstream = (int)v;
             break;
         case HGM_OPT_FUSED_VSDEPTH:
-            if (!(v == 2 || v == 3 || v == 4)) return bad("fused_vsdepth is 2, 3 or 4");
+            if (v == 4) return bad(kRetiredMsg);
+            if (!(v == 2 || v == 3)) return bad("fused_vsdepth is 2 or 3");
             n.fused_vsdepth = (int)v;
             break;
         case HGM_OPT_PERT_SHARED: if (!b01) return bad("pert_shared is 0 or 1"); n.pert_shared = v != 0; break;
@@ -619,6 +592,7 @@ HGM_API int hgm_ctx_set_option(hgm_ctx* c, int option, double v) {
 HGM_API int hgm_ctx_get_option(const hgm_ctx* c, int option, double* v) {
     if (!c || !v) return HGM_E_ARG;
     const hgm::Numerics& n = c->num;
+    if (retired_option(option, v)) return HGM_OK;
     switch (option) {
         case HGM_OPT_PARITY: *v = n.parity; break;
         case HGM_OPT_MGS_FORM: *v = n.mgs_form; break;
@@ -638,18 +612,8 @@ HGM_API int hgm_ctx_get_option(const hgm_ctx* c, int option, double* v) {
         case HGM_OPT_PAGED16: *v = n.paged16; break;
         case HGM_OPT_BAND_DUAL: *v = n.band_dual; break;
         case HGM_OPT_FUSED_AB: *v = n.fused_ab; break;
-        case HGM_OPT_FUSED_REGION: *v = n.fused_region; break;
-        case HGM_OPT_FUSED_BS: *v = n.fused_bs; break;
-        case HGM_OPT_FUSED_DBG: *v = n.fused_dbg; break;
-        case HGM_OPT_FUSED_PF: *v = n.fused_pf; break;
         case HGM_OPT_KRYLOV_PAD: *v = n.krylov_pad; break;
-        case HGM_OPT_FUSED_KIND: *v = n.fused_kind; break;
         case HGM_OPT_FUSED_WREGION: *v = n.fused_wregion; break;
-        case HGM_OPT_FUSED_WAVES: *v = n.fused_waves; break;
-        case HGM_OPT_FUSED_GROUP: *v = n.fused_group; break;
-        case HGM_OPT_FUSED_DEPTH: *v = n.fused_depth; break;
-        case HGM_OPT_FUSED_PAIRS: *v = n.fused_pairs; break;
-        case HGM_OPT_FUSED_ACC32: *v = n.fused_acc32; break;
         case HGM_OPT_FUSED_PLAN_DEV: *v = n.fused_plan_dev; break;
         case HGM_OPT_FUSED_REDUCE: *v = n.fused_reduce; break;
         case HGM_OPT_FUSED_ROWPAIR: *v = n.fused_rowpair; break;

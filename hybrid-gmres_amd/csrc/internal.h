@@ -15,20 +15,6 @@
 #include "dispatch.h"
 #include "hgmres.h"
 
-// Measured variants of the one-pass kernel (the kind-0 sub-chunk pass, row-pair modes 1-3, other
-// wave / batch / depth / pairing shapes, other fp32 accumulations and reductions, the phase-skipping
-// timing bits) are compiled only into an experiments build (make EXTRA=-DHGM_EXPERIMENTS=1, used by
-// scripts/fused_micro.py); the default library carries the production kernels alone and refuses
-// those option values (hgm_ctx_set_option, hgm_experiments()).
-#ifndef HGM_EXPERIMENTS
-#define HGM_EXPERIMENTS 0
-#endif
-// Load-ring depth of the compact one-pass kernel (HGM_OPT_FUSED_VSDEPTH): the default library carries
-// depth 2 and this one, the experiments build 2, 3 and 4 (DESIGN.md §3.5 has the depth table).
-#ifndef HGM_VSDEPTH_DEFAULT
-#define HGM_VSDEPTH_DEFAULT 3
-#endif
-
 namespace hgm {
 
 struct Error {
@@ -95,28 +81,18 @@ struct Numerics {
     bool paged16 = true;            // streaming SpMV: paged gathers also for 16-bit-index operators
     bool band_dual = true;          // banded tiled ray-major operators: steep rows in row strips
     bool fused_ab = true;           // m-space operator A*(B*q) in one pass over B (fused.hip)
-    int fused_region = 64;          // ... pixel square per workgroup (its rays accumulate in LDS)
-    int fused_bs = 1024;            // ... threads per workgroup (512, 1024)
-    int fused_pf = 2;               // ... sub-chunk batches in registers (pipeline depth 1..4)
-    int fused_kind = 1;             // ... 0 sub-chunk pass, 1 row-wave pass
-    int fused_wregion = 32;         // ... row-wave pass: pixel square per workgroup
-    int fused_waves = 4;            // ... row-wave pass: waves per workgroup (1, 2, 4)
-    int fused_group = 8;            // ... row-wave pass: rows per load batch (4, 8)
-    int fused_depth = 2;            // ... row-wave pass: batches in the load ring (2..4)
-    bool fused_pairs = true;        // ... row-wave pass: two entries per lane
-    int fused_acc32 = 1;            // ... fp32 row-wave pass: 0 ds_add_f32, 1 read-add-write, 2 fp64 accumulators
-    bool fused_plan_dev = true;     // ... row-wave plan's ray sets built on the device (false: the host build)
-    int fused_rowpair = 4;          // ... row-wave pass: units of two consecutive rows per chunk (k_fused_rw RP 1-4)
-    int fused_vstream = 1;          // ... row-wave pass, fp64 row-pair mode 4: compact value stream with in-slot codes
+    int fused_wregion = 32;         // ... pixel square per workgroup (its rays accumulate in LDS)
+    bool fused_plan_dev = true;     // ... the plan's ray sets built on the device (false: the host build)
+    int fused_rowpair = 4;          // ... units of two consecutive rows per chunk (0 single rows, 4 pairs; k_fused_rw PAIRS)
+    int fused_vstream = 1;          // ... fp64 row pairs: compact value stream with in-slot codes
                                     //     (0 plain, 1 when it saves enough bytes, 2 / 3 measurement forms; fused.hip)
-    int fused_vsdepth = HGM_VSDEPTH_DEFAULT;   // ... the compact pass's own load ring (2..4; the other passes keep fused_depth)
-    int fused_reduce = 0;           // ... row-wave partial reduction: 0 by ray (rs_slot), 1 by ray band (runs;
+    int fused_vsdepth = 3;          // ... the compact pass's own load ring (2 or 3: DESIGN.md §3.5 has the depth table)
+    int fused_reduce = 0;           // ... partial reduction: 0 by ray (rs_slot), 1 by ray band (runs;
                                     //     bitwise equal, measured 2-4% slower pass at C4, profiles/r4_c4_reduce_band_ab.jsonl)
     bool lsqr_res_img = true;       // one-pass LSQR: final residual from the A*x image (no SpMV)
     bool lsmr_fuse_nmon = true;     // one-pass fp32 LSMR: the n-space step and monitor in one launch
     bool pert_shared = true;        // perturbed product: shared index stream when E has B0's pattern (spmm.hip)
     int krylov_pad = -1;           // Krylov basis column padding (elements; -1 auto, kernels.hip krylov_ld)
-    int fused_dbg = 0;              // ... timing experiments: skip phases (wrong results)
 };
 struct FusedPlan;
 
@@ -707,15 +683,13 @@ std::vector<int64_t> pix_reference_of_stored(const PixOrder& o);
 // pair / context does not qualify (the two-pass path then runs).
 bool fused_ab_eligible(const hgm_ctx* c, const hgm_mat* A, const hgm_mat* B);
 const FusedPlan* fused_ab_plan(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B);
-// With xt and zx_out (the row-wave kernel only; returns whether it did): also *zx_out =
+// With xt and zx_out (returns whether it did): also *zx_out =
 // x_true'(B*q), the m-space Gram error monitor's side dot, from the row sums as they form.
-// With pn (pn->np > 0, fused_pend_ok): q still holds the unnormalised v of the previous MGS sweep,
+// With pn (pn->np > 0): q still holds the unnormalised v of the previous MGS sweep,
 // and the pass applies q = v / h itself (FusedArgs::pn).
 bool fused_ab(hgm_ctx* c, const hgm_mat* B, const FusedPlan* P, const double* q, double* Bq, double* ABq,
               const double* xt = nullptr, double* zx_out = nullptr, const PendNorm<double>* pn = nullptr);
-// whether the pass takes the pending normalisation of q for this plan (the row-wave kernel)
-bool fused_pend_ok(const hgm_ctx* c, const FusedPlan* P);
-// The general pass (T = double or float; fp32 and every epilogue: the row-wave kernel).  Over B's
+// The general pass (T = double or float).  Over B's
 // rows j (pixels) and columns i (rays):
 //   z_j = B(j,:) q ; zs_j = z_j - a ev_j with a = (T)sqrt((double)*easq) (no ev: zs = z) ;
 //   zraw = z, zout = zs (either optional; zout may alias ev) ; w_i = sum_j B(j,i) zs_j ;
@@ -734,7 +708,7 @@ struct FusedArgs {
     T* zout = nullptr;
     bool side_sq = false;
     T* side_out = nullptr;
-    // pending normalisation of q (pn.np > 0: the row-wave pass, fused_pend_ok): q = v / h
+    // pending normalisation of q (pn.np > 0): q = v / h
     // with h = sqrt(sum of pn.parts), published to pn.hdev and pn.hring (fused.hip k_fused_rw)
     PendNorm<T> pn;
 };
@@ -753,12 +727,6 @@ bool fused_plan_device_built(const FusedPlan* P);
 // B's entries that carry a dictionary code, the bytes of the compact values, the plan's device bytes
 void fused_plan_vstream_info(const FusedPlan* P, int* active, double* coverage, int64_t* value_bytes,
                              int64_t* plan_bytes);
-
-// Solver entry check: HGM_OPT_FUSED_DBG skips phases of the one-pass kernel (timing experiments of
-// hgm_spmv_ab only, scripts/fused_micro.py): a solve would return wrong results, so it is refused.
-inline void solver_guard(const hgm_ctx* c) {
-    HGM_REQUIRE(c->num.fused_dbg == 0, "fused_dbg is a timing experiment (hgm_spmv_ab only): set it to 0 to solve");
-}
 
 // ---------------- comm / scalars (capi.cpp) ----------------
 void allreduce(hgm_ctx* c, double* dev, int64_t count);

@@ -387,7 +387,6 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
                  const double* b_in, const double* xt_in, double tol, int maxit, double lambda, double* x_out,
                  double* err_out, double* res_out, int* niters, KrylovBasis* basis_out) {
     check_dims(A, B);
-    solver_guard(c);
     HGM_REQUIRE(B != nullptr, "B is NULL");
     const PixOrder po = n_order(c, A, B);
     HGM_REQUIRE(b_in != nullptr && xt_in != nullptr, "b and x_true are required");
@@ -576,8 +575,7 @@ int gmres_family(hgm_ctx* c, const GmresSpec& sp, const hgm_opts* o, const hgm_m
     // measured ~1.4 % slower at C4 than the scale pass it replaces)
     const bool pn_ok = !dist && orth == HGM_MGS && c->num.pend_norm >= 1 && !parity &&
                        (nspace ? spmv_pn_ok(A, EPI_DIVH) && spmv_pn_ok(B, EPI_ADDQ)
-                               : c->num.pend_norm == 2 && fplan != nullptr && fused_pend_ok(c, fplan) &&
-                                     !krylov_padded(c, ldq));
+                               : c->num.pend_norm == 2 && fplan != nullptr && !krylov_padded(c, ldq));
     PendNorm<double> pend;                                  // np > 0: Q(:,next step) awaits its division
     double* pn_h = c->buf<double>("pn_h", 2);
     // Enqueue Arnoldi step kq: operator application + orthogonalisation (+ Gram column).
@@ -940,7 +938,6 @@ int lsqr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
            const double* xt_in, double tol, int maxit, bool hybrid, double lambda, double* x_out,
            double* err_out, double* res_out, int* niters) {
     check_dims(A, At);
-    solver_guard(c);
     HGM_REQUIRE(At != nullptr, "At is NULL");
     const PixOrder po = n_order(c, A, At);
     HGM_REQUIRE(b_in != nullptr && xt_in != nullptr, "b and x_true are required");
@@ -1185,7 +1182,6 @@ int lsmr_t(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* At, c
            const double* xt_in, double tol, int maxit, double* x_out, double* err_out, double* res_out,
            double* ar_out, int* iters) {
     check_dims(A, At);
-    solver_guard(c);
     HGM_REQUIRE(At != nullptr, "At is NULL");
     const PixOrder po = n_order(c, A, At);
     HGM_REQUIRE(b_in != nullptr, "b is required");
@@ -1442,7 +1438,6 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
                 const double* xt_in, double tol, int maxit, double lambda, double* x_out, double* err_out,
                 double* res_out, int* niters) {
     check_dims(A, At);
-    solver_guard(c);
     HGM_REQUIRE(At != nullptr, "At is NULL");
     const PixOrder po = n_order(c, A, At);
     HGM_REQUIRE(A->dtype == HGM_F64, "hybrid LSMR is fp64");
@@ -1524,7 +1519,6 @@ int hybrid_lsmr(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* 
 int arnoldi(hgm_ctx* c, const hgm_mat* A, const hgm_mat* B, const double* b_in, int kg, int side,
             double btol, int orth, double* H_out, double* beta_out, int* kdone) {
     check_dims(A, B);
-    solver_guard(c);
     HGM_REQUIRE(B != nullptr, "B is NULL");
     (void)n_order(c, A, B);   // H does not depend on the stored pixel order (up to rounding)
     HGM_REQUIRE(A->dtype == HGM_F64, "Arnoldi is fp64");
@@ -1593,7 +1587,6 @@ int gmres_bounds_sweep(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hg
                        double* X_out, double* err_surf, double* res_surf, double* sol_surf, int* niters,
                        int* ksteps) {
     check_dims(A, B);
-    solver_guard(c);
     HGM_REQUIRE(B != nullptr, "B is NULL");
     HGM_REQUIRE(b_in != nullptr, "b is required");
     HGM_REQUIRE(A->dtype == HGM_F64, "lambda sweep: fp64 operators only");
@@ -2090,7 +2083,6 @@ int lockstep_core(hgm_ctx* c, const Lockstep& L, int orth, double* H_out, const 
 // the refusals every lockstep entry point shares
 void lockstep_guard(hgm_ctx* c, const hgm_opts* o, const hgm_mat* A, const hgm_mat* B, const std::string& what) {
     check_dims(A, B);
-    solver_guard(c);
     HGM_REQUIRE(B != nullptr, "B is NULL");
     HGM_REQUIRE(A->dtype == HGM_F64, what + ": fp64 operators only");
     if (dist_n(c) || c->host_ar != nullptr)

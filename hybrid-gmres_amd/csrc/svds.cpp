@@ -31,7 +31,6 @@ namespace hgm {
 int svds(hgm_ctx* c, const hgm_mat* A, const hgm_mat* At, const double* b_in, int steps, int nsv, double btol,
          const double* X, int64_t ldx, int nx, double* sigma, double* resid, double* utb, double* VtX, double* U_out,
          int64_t ldu_out, double* V_out, int64_t ldv_out, int* steps_done) {
-    solver_guard(c);
     HGM_REQUIRE(A != nullptr && At != nullptr, "svds: A and At are required");
     HGM_REQUIRE(A->dtype == HGM_F64 && At->dtype == HGM_F64, "svds: fp64 operators only");
     HGM_REQUIRE(!c->num.parity, "svds: not in parity mode");

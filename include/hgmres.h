@@ -147,33 +147,33 @@ enum hgm_ctx_option {
                                       of one: on a communicator every rank runs it on its shard, followed by
                                       the m-vector all-reduce) [1]: the kept B*q and A*(B*q) come out of one
                                       kernel (plan built on first use) */
-    /* [experiments] options 19-22, 24, 26-30 and the marked values of 32, 34 and 38 select measured
-     * variants of the one-pass kernel (DESIGN.md §3.5 records each measurement): only an experiments
-     * build (hgm_experiments() == 1) has their kernels; the default library accepts only the
-     * production value in brackets. */
-    HGM_OPT_FUSED_REGION = 19,     /* [experiments] kind-0 pass: pixel square per workgroup [64] */
-    HGM_OPT_FUSED_BS = 20,         /* [experiments] kind-0 pass: 512 or 1024 threads [1024] */
-    HGM_OPT_FUSED_DBG = 21,        /* [experiments] timing only: bits skip the pass's phases, results WRONG;
-                                      hgm_spmv_ab only, every solver refuses it [0] */
-    HGM_OPT_FUSED_PF = 22,         /* [experiments] kind-0 pass: sub-chunk batches in registers 1..4 [2] */
+    /* [retired] options 19-22, 24, 26-30 and the marked values of 32, 34 and 38 selected measured
+     * variants of the one-pass kernel (DESIGN.md §3.5 records each measurement).  Their kernels are
+     * retired: the numbers stay, the library accepts only the production value in brackets (a no-op)
+     * and refuses every other value with HGM_E_ARG.  Commit 9d41033 is the last tree that builds the
+     * variants (make EXTRA=-DHGM_EXPERIMENTS=1). */
+    HGM_OPT_FUSED_REGION = 19,     /* [retired] kind-0 pass: pixel square per workgroup [64] */
+    HGM_OPT_FUSED_BS = 20,         /* [retired] kind-0 pass: 512 or 1024 threads [1024] */
+    HGM_OPT_FUSED_DBG = 21,        /* [retired] timing only: bits skipped the pass's phases [0] */
+    HGM_OPT_FUSED_PF = 22,         /* [retired] kind-0 pass: sub-chunk batches in registers 1..4 [2] */
     HGM_OPT_KRYLOV_PAD = 23        /* elements added to the Krylov basis' leading dimension when it
                                       is a multiple of 4096 (a power-of-two column stride sends
                                       every column's element i to the same HBM channel) [-1 = auto] */,
-    HGM_OPT_FUSED_KIND = 24,       /* [experiments] kernel of the one-pass A*(B*q): 0 the sub-chunk pass
+    HGM_OPT_FUSED_KIND = 24,       /* [retired] kernel of the one-pass A*(B*q): 0 the sub-chunk pass
                                       (options 19-22), 1 the row-wave pass [1] */
     HGM_OPT_FUSED_WREGION = 25,    /* ... row-wave pass: pixel square (side) per workgroup [32] */
-    HGM_OPT_FUSED_WAVES = 26,      /* [experiments] row-wave pass: waves per workgroup, 1, 2 or 4 [4] */
-    HGM_OPT_FUSED_GROUP = 27,      /* [experiments] row-wave pass: pixel rows per load batch, 4 or 8 [8] */
-    HGM_OPT_FUSED_DEPTH = 28,      /* [experiments] row-wave pass: batches in its load ring, 2..4 [2] */
-    HGM_OPT_FUSED_PAIRS = 29,      /* [experiments] row-wave pass: two entries per lane [1] */
-    HGM_OPT_FUSED_ACC32 = 30       /* [experiments] fp32 pass (lsqr_solver / lsmr_solver of configs[4]): how a
+    HGM_OPT_FUSED_WAVES = 26,      /* [retired] row-wave pass: waves per workgroup, 1, 2 or 4 [4] */
+    HGM_OPT_FUSED_GROUP = 27,      /* [retired] row-wave pass: pixel rows per load batch, 4 or 8 [8] */
+    HGM_OPT_FUSED_DEPTH = 28,      /* [retired] row-wave pass: batches in its load ring, 2..4 [2] */
+    HGM_OPT_FUSED_PAIRS = 29,      /* [retired] row-wave pass: two entries per lane [1] */
+    HGM_OPT_FUSED_ACC32 = 30       /* [retired] fp32 pass (lsqr_solver / lsmr_solver of configs[4]): how a
                                       region's rays accumulate: 0 ds_add_f32, 1 fp32 read-add-write,
                                       2 fp64 accumulators and partials [1] */,
     HGM_OPT_FUSED_PLAN_DEV = 31,   /* ... the row-wave plan's region ray sets and slots built on the device
                                       (an LDS bitmap per region) [1]; 0 the host build (same bytes) */
     HGM_OPT_FUSED_REDUCE = 32,     /* ... the row-wave pass's partial reduction: 1 by bands of 64 rays over
                                       runs of consecutive slots, 0 per ray through its slot list [0] (the
-                                      same sums: bitwise equal); [experiments] 2, 3, 4: per ray with 1, 2
+                                      same sums: bitwise equal); [retired] 2, 3, 4: per ray with 1, 2
                                       or 4 lanes per ray instead of 8 (another fixed order) */
     HGM_OPT_HOST_SPIN_US = 33      /* host waits (stream / event / ring polls): microseconds of pure spinning
                                       before each further poll yields the core (sched_yield) [200; -1 when
@@ -183,7 +183,7 @@ enum hgm_ctx_option {
     HGM_OPT_FUSED_ROWPAIR = 34     /* ... row-wave pass: two consecutive pixel rows per 128-entry chunk [4]:
                                       0 one row per chunk; 4 the second row right after the first, one
                                       accumulator array per wave, the two rows' q reads and adds by two
-                                      instructions each (other lanes on their dummy slot); [experiments]
+                                      instructions each (other lanes on their dummy slot); [retired]
                                       1 (a private array per row parity), 2 (the second row from the lane
                                       after the first row's last pair), 3 (the row split by selects of the
                                       products): the 2048-slot shape only */,
@@ -201,10 +201,10 @@ enum hgm_ctx_option {
                                       §3.5; otherwise the plain plan, bit-identical to 0), 3 compact whenever
                                       the plan's shape allows it, 2 as 3 with an empty dictionary (every value
                                       stored: the decode overhead measurement) */,
-    HGM_OPT_FUSED_VSDEPTH = 38     /* ... the compact pass of option 37 only: batches in ITS load ring, 2, 3 or
-                                      4 [3] (every other pass keeps option 28's depth 2; the same bits at
-                                      every depth; 3 is 1 % faster than 2 at C4).  The default
-                                      library carries 2 and 3; [experiments] 4 (measured slower) */,
+    HGM_OPT_FUSED_VSDEPTH = 38     /* ... the compact pass of option 37 only: batches in ITS load ring, 2 or
+                                      3 [3] (every other pass keeps depth 2; the same bits at every depth;
+                                      3 is 1 % faster than 2 at C4); [retired] 4 (measured
+                                      slower) */,
     HGM_OPT_PERT_SHARED = 39       /* perturbed product (hgm_spmm_pert, hgm_gmres_bounds_mismatch, hgm_arnoldi_mismatch):
                                       when E has B0's sparsity pattern, one index stream and one x gather per
                                       entry serve both value streams [1]; 0 forces the general two-pattern walk
@@ -217,9 +217,9 @@ typedef int (*hgm_allreduce_fn)(double* buf, int64_t count, void* user);
 
 /* ---- context ---------------------------------------------------------- */
 HGM_API int hgm_version(void);
-/* 1 for an experiments build (make EXTRA=-DHGM_EXPERIMENTS=1), which also carries the measured
- * variants of the one-pass kernel that the options marked [experiments] below select; the default
- * library (0) has the production kernels only and refuses those values with HGM_E_ARG. */
+/* Always 0.  It told an experiments build, which carried the measured variants of the one-pass
+ * kernel behind the options now marked [retired], from the default library; those variants are
+ * retired and the call stays for its callers. */
 HGM_API int hgm_experiments(void);
 /* Number of distinct HIP runtime files (libamdhip64*) mapped into the process, their paths
  * ';'-separated in msg.  More than one (e.g. PyTorch's bundled copy loaded AFTER this library

@@ -1,7 +1,13 @@
 """Micro-benchmark of the m-space operator A*(B*q) (hgm_spmv_ab) at a BASELINE geometry: the
-one-pass kernel (fused.hip) against the two SpMVs, and phase-skip timing variants (fused_dbg:
-results wrong, timing only).  Prints one JSON line per variant.  Run on the GPU box:
+one-pass kernel (fused.hip) against the two SpMVs.  Prints one JSON line per variant.  Run on the
+GPU box:
     python scripts/fused_micro.py [N angles reps [variants]]
+Variants (comma-separated): `two` (the two SpMVs, the reference of the deviations) or
+[w4]r<region>[q<0|4>][s<0-3>][v<2|3>]: the one pass (four waves) with that region side (fused_wregion), row pairs
+(fused_rowpair, default 4), compact value stream mode (fused_vstream, default 1) and the compact
+pass's ring depth (fused_vsdepth, default 3).  The other variants this script once timed (the
+sub-chunk pass, wave / batch / depth shapes, fp32 accumulations, phase skips) are retired with
+their kernels; DESIGN.md §3.5 keeps their measurements.
 HGM_MICRO_F32=1: the fp32 operator (BASELINE configs[4]; the fp32 one-pass kernel)."""
 import ctypes as C
 import json
@@ -18,7 +24,24 @@ import hgmres  # noqa: E402
 from hgmres import _lib as L  # noqa: E402
 
 N, na, reps = (int(a) for a in (sys.argv[1:4] if len(sys.argv) > 3 else (4096, 47, 20)))
-variants = sys.argv[4].split(",") if len(sys.argv) > 4 else ["two", "f1024", "f512", "d1", "d2", "d4", "d8", "d15"]
+variants = sys.argv[4].split(",") if len(sys.argv) > 4 else ["two", "r32", "r32q0", "r32s0", "r32v2"]
+
+
+def variant_options(vname):
+    mw = re.fullmatch(r"(?:w4)?r(\d+)(?:q([04]))?(?:s([0-3]))?(?:v([23]))?", vname)
+    if vname == "two":
+        return dict(fused_ab=0)
+    if not mw:
+        sys.exit(f"fused_micro: unknown variant {vname!r}: two, or [w4]r<region>[q<0|4>][s<0-3>][v<2|3>] "
+                 "(the other variants are retired: DESIGN.md §3.5)")
+    o = dict(fused_ab=1, fused_wregion=int(mw.group(1)))
+    for name, val in (("fused_rowpair", mw.group(2)), ("fused_vstream", mw.group(3)), ("fused_vsdepth", mw.group(4))):
+        if val is not None:
+            o[name] = int(val)
+    return o
+
+
+options = [variant_options(v) for v in variants]      # (a typo fails before anything runs)
 ctx = hgmres.Context(0)
 lib = L.load()
 f32 = os.environ.get("HGM_MICRO_F32", "0") == "1"
@@ -34,31 +57,7 @@ P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
 s_ = 4.0 if f32 else 8.0
 two = 2 * (s_ + 4) * A.nnz + 8.0 * (m + 1) + 8.0 * (n + 1) + 2 * s_ * (m + n)
 ref = None
-for vname in variants:
-    # two | f<threads>[x<depth>][r<region>] (fused, pipeline depth [2], region side [64])
-    # | d<bits> (phase-skip timing)
-    mf = re.fullmatch(r"f(\d+)(?:x(\d))?(?:r(\d+))?", vname)
-    # row-wave pass: waves, region, rows per batch, ring depth, pairs
-    # (v<depth>: the compact value stream, forced on, with that depth of its own load ring)
-    mw = re.fullmatch(r"w(\d)r(\d+)(?:g(\d+))?(?:d(\d))?(?:p(\d))?(?:a(\d))?(?:q(\d))?(?:v(\d))?", vname)
-    if vname.startswith("e"):                                   # row-wave pass, phase-skip timing
-        o = dict(fused_ab=1, fused_kind=1, fused_dbg=int(vname[1:]), fused_acc32=1)
-    elif mw:
-        o = dict(fused_ab=1, fused_kind=1, fused_waves=int(mw.group(1)), fused_wregion=int(mw.group(2)),
-                 fused_group=int(mw.group(3) or 8), fused_depth=int(mw.group(4) or 2),
-                 fused_pairs=int(mw.group(5) or 1), fused_acc32=int(mw.group(6) or 1),
-                 fused_rowpair=int(mw.group(7) or 0))
-        if mw.group(8):
-            o.update(fused_vstream=3)
-            if "fused_vsdepth" in L.OPTIONS_37 and lib.hgm_ctx_get_option(ctx.handle, 38, C.byref(C.c_double())) == 0:
-                o.update(fused_vsdepth=int(mw.group(8)))     # (a library from before option 38: its depth 2)
-    elif vname == "two":
-        o = dict(fused_ab=0)
-    elif mf:
-        o = dict(fused_ab=1, fused_kind=0, fused_bs=int(mf.group(1)), fused_pf=int(mf.group(2) or 2),
-                 fused_region=int(mf.group(3) or 64))
-    else:
-        o = dict(fused_ab=1, fused_kind=0, fused_dbg=int(vname[1:]))
+for vname, o in zip(variants, options):
     with ctx.options(**o):
         lib.hgm_spmv_ab(ctx.handle, A._h, B._h, P(q), P(bq), P(abq))      # plan / warm-up
         ctx.synchronize()

@@ -7,7 +7,9 @@ symbol name) and hashes, per kernel symbol, its instructions (comments dropped, 
 of local labels dropped: emission order may differ between two trees) and its
 .amdhsa_kernel ... .end_amdhsa_kernel block (registers, LDS, scratch).  Two trees carry the same
 device code when their listings are equal.  --brief prints one line per unit instead: the unit, its
-kernel count and the sha256 of its per-kernel lines (what profiles/ keeps):
+kernel count and the sha256 of its per-kernel lines (what profiles/ keeps).  --anonymous compares
+trees whose kernels were renamed (other template parameters, the same instructions): each kernel is
+hashed with its own symbol replaced by a fixed token and the lines are printed sorted, without names:
 
     python scripts/kernel_listing.py hybrid-gmres_amd/csrc > branch.txt
     python scripts/kernel_listing.py ../parent/hybrid-gmres_amd/csrc > parent.txt && cmp parent.txt branch.txt
@@ -45,8 +47,9 @@ def normal(lines):
     return hashlib.sha256("\n".join(keep).encode()).hexdigest()[:16]
 
 
-def kernels(lines):
-    """{kernel: (body hash, descriptor hash)} of one unit's assembly"""
+def kernels(lines, anonymous=False):
+    """{kernel: (body hash, descriptor hash)} of one unit's assembly; anonymous: with the kernel's own
+    symbol (the .size / .set lines of the body, the .amdhsa_kernel line) replaced by a fixed token"""
     start = {}
     for i, ln in enumerate(lines):
         m = re.match(r"([A-Za-z_][\w.$]*):", ln)
@@ -62,7 +65,11 @@ def kernels(lines):
                 j += 1
             name = m.group(1)
             body = [ln for ln in lines[start[name] + 1:i] if not re.match(r"\s*\.(section|p2align)\b", ln)]
-            found[name] = (normal(body), normal(lines[i:j + 1]))
+            desc = lines[i:j + 1]
+            if anonymous:
+                own = re.compile(r"(?<![\w.$])" + re.escape(name) + r"(?![\w$])")
+                body, desc = ([own.sub("KERNEL", ln) for ln in part] for part in (body, desc))
+            found[name] = (normal(body), normal(desc))
             i = j
         i += 1
     return found
@@ -83,12 +90,19 @@ def main():
     ap.add_argument("--extra", default="", help="further compiler flags, e.g. -DHGM_EXPERIMENTS=1")
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("--brief", action="store_true", help="one line per unit: kernel count and hash of its lines")
+    ap.add_argument("--anonymous", action="store_true",
+                    help="hash each kernel without its own symbol and list sorted (unit, body, descriptor) lines "
+                         "without names: equal multisets = the same kernels under other names")
     a = ap.parse_args()
     units = a.units or sorted(u for u in os.listdir(a.csrc) if u.endswith(".hip"))
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
         texts = list(pool.map(lambda u: assembly(a.csrc, u, a.extra.split(), tmp), units))
-    listing = [f"{unit} {name} {body} {desc}" for unit, lines in zip(units, texts)
-               for name, (body, desc) in sorted(kernels(lines).items())]
+    if a.anonymous:
+        listing = sorted(f"{unit} {body} {desc}" for unit, lines in zip(units, texts)
+                         for body, desc in kernels(lines, True).values())
+    else:
+        listing = [f"{unit} {name} {body} {desc}" for unit, lines in zip(units, texts)
+                   for name, (body, desc) in sorted(kernels(lines).items())]
     print("\n".join(brief(listing) if a.brief else listing))
 
 

@@ -35,7 +35,7 @@ def main():
         res = {}
         regions = [int(r) for r in sys.argv[3].split(",")] if len(sys.argv) > 3 else []
         runs = [("two", dict(fused_ab=0)), ("fused", dict(fused_ab=1)), ("two_b", dict(fused_ab=0)),
-                ("fused_b", dict(fused_ab=1))] + [(f"fused_r{r}", dict(fused_ab=1, fused_region=r)) for r in regions]
+                ("fused_b", dict(fused_ab=1))] + [(f"fused_r{r}", dict(fused_ab=1, fused_wregion=r)) for r in regions]
         for name, o in runs:
             with ctx.options(**o):
                 assert lib.hgm_spmv_ab(ctx.handle, A_g._h, B_g._h, P(q), P(bq), P(abq)) == 0   # plan / warm-up

@@ -8,9 +8,8 @@ in another fixed order than the two-pass kernels', so:
   * B*q itself (the kept column, read by x = (B*Q) y): within rounding of the two-pass product,
   * pixel grids whose side is not a multiple of the region, several region sizes, and a region
     crossed by more rays than the LDS holds (the plan is refused: the two-pass path runs).
-Two kernels do the pass (HGM_OPT_FUSED_KIND): the sub-chunk pass (kind 0) and the row-wave pass
-(kind 1, the default); both are held to the same bars over several region shapes, waves and row
-batches.
+The row-wave kernel does the pass; it is held to these bars over several region shapes.  (The
+sub-chunk pass and the other wave / batch / depth / pairing shapes are retired: DESIGN.md §3.5.)
 The full-size check (C4, 1e9 nnz, 20 iterations vs the oracle fixture) is
 tests/test_gpu_fullsize.py::test_c4_ab_gmres_full_size, which runs with the fused pass on (default).
 """
@@ -42,41 +41,19 @@ def _device_problem(ctx, N, na, seed=0):
     return A, A.T, b0 + e / np.linalg.norm(e) * 1e-2 * np.linalg.norm(b0), xt
 
 
-# (N, angles, kind, region, waves, rows per batch, ring depth, pairs): kind 0 the sub-chunk pass
-# (fused_region), kind 1 the row-wave pass (fused_wregion / _waves / _group / _depth / _pairs);
-# the row-wave variants other than the default (8 rows, depth 2, pairs) exist for 4 waves and
-# <= 1,984 rays per region (the 32 x 32 regions at 47 angles)
-CASES = [(512, 30, 0, 64, 0, 0, 0, 0), (100, 17, 0, 64, 0, 0, 0, 0), (256, 47, 0, 32, 0, 0, 0, 0),
-         (256, 47, 0, 16, 0, 0, 0, 0), (128, 90, 0, 24, 0, 0, 0, 0),
-         (512, 30, 1, 32, 4, 8, 2, 1), (100, 17, 1, 32, 4, 8, 2, 1), (256, 47, 1, 24, 4, 8, 2, 1),
-         (256, 47, 1, 16, 1, 8, 2, 1), (256, 47, 1, 32, 2, 8, 2, 1), (128, 90, 1, 16, 2, 8, 2, 1),
-         (200, 60, 1, 20, 1, 8, 2, 1), (256, 47, 1, 32, 4, 4, 3, 1), (256, 47, 1, 32, 4, 8, 3, 1),
-         (256, 47, 1, 32, 4, 4, 2, 1), (256, 47, 1, 32, 4, 8, 2, 0), (256, 47, 1, 32, 4, 4, 2, 0)]
-
-
-def _experiments():
-    from hgmres import _lib as L
-    return bool(L.load().hgm_experiments())
-
-
-def _variant_only_in_experiments(is_variant):
-    """Measured variants of the one-pass kernel (kind 0, other wave / batch / depth / pairing
-    shapes, row-pair modes 1-3) are compiled into the experiments build only (HGM_EXPERIMENTS=1;
-    run these cases with HGM_LIB pointing at it); the default library refuses their option values."""
-    if is_variant and not _experiments():
-        pytest.skip("measured variant of the one-pass kernel: experiments build only")
+# (N, angles, kind, region, waves, rows per batch, ring depth, pairs): the row-wave pass (kind 1) in
+# its one shape (4 waves, 8 rows, depth 2, pairs; the option values are the production ones, which
+# the library accepts as no-ops) over fused_wregion
+CASES = [(512, 30, 1, 32, 4, 8, 2, 1), (100, 17, 1, 32, 4, 8, 2, 1), (256, 47, 1, 24, 4, 8, 2, 1)]
 
 
 def _fused_opts(kind, region, waves=4, group=8, depth=2, pairs=1):
-    if kind == 0:
-        return dict(fused_ab=1, fused_kind=0, fused_region=region)
-    return dict(fused_ab=1, fused_kind=1, fused_wregion=region, fused_waves=waves, fused_group=group,
+    return dict(fused_ab=1, fused_kind=kind, fused_wregion=region, fused_waves=waves, fused_group=group,
                 fused_depth=depth, fused_pairs=pairs)
 
 
 @pytest.mark.parametrize("N,na,kind,region,waves,group,depth,pairs", CASES)
 def test_fused_ab_matches_two_pass_and_oracle(gpu_ctx, N, na, kind, region, waves, group, depth, pairs):
-    _variant_only_in_experiments(kind == 0 or (waves, group, depth, pairs) != (4, 8, 2, 1))
     A, B, b, xt = _device_problem(gpu_ctx, N, na)
     k = 20
     with gpu_ctx.options(fused_ab=0):
@@ -85,11 +62,6 @@ def test_fused_ab_matches_two_pass_and_oracle(gpu_ctx, N, na, kind, region, wave
         out = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, k, ctx=gpu_ctx, return_H=True)
         again = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, k, ctx=gpu_ctx, return_H=True)
         hyb = hgmres.ABgmres_hybrid_bounds(A, B, b, xt, 0.0, k, 1e-2, ctx=gpu_ctx, return_H=True)
-        if kind == 0:
-            # the workgroup-size variant keeps the summation order: the same bits
-            with gpu_ctx.options(fused_bs=512):
-                o2 = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, k, ctx=gpu_ctx, return_H=True)
-            assert all(np.array_equal(np.asarray(a_), np.asarray(b_)) for a_, b_ in zip(out, o2))
     with gpu_ctx.options(fused_ab=0):
         hyb2 = hgmres.ABgmres_hybrid_bounds(A, B, b, xt, 0.0, k, 1e-2, ctx=gpu_ctx, return_H=True)
     for a_, b_ in zip(out, again):
@@ -134,35 +106,29 @@ def test_fused_pass_stress_repeat_bitwise(gpu_ctx, N, na, dtype):
     B.close()
 
 
-@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("kind", [1])
 def test_fused_region_overflow_falls_back(gpu_ctx, kind):
-    """A 128 x 128 region at 47 angles is crossed by ~7,700 rays (> the 3,968 LDS accumulators of
-    the sub-chunk pass); a 64 x 64 region by ~3,900 (> the 1,984 ray slots of four row waves):
-    the plan is refused and the two-pass path gives the result, bit for bit."""
-    _variant_only_in_experiments(kind == 0)
+    """A 64 x 64 region at 47 angles is crossed by ~3,900 rays (> the 1,984 ray slots of four row
+    waves): the plan is refused and the two-pass path gives the result, bit for bit."""
     A, B, b, xt = _device_problem(gpu_ctx, 256, 47)
     with gpu_ctx.options(fused_ab=0):
         ref = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
-    if kind == 1:
-        # the row-wave plan retries a refused region with half its side (round 5): 64 -> 32, the
-        # default plan, bit for bit
-        with gpu_ctx.options(**_fused_opts(1, 64)):
-            out = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
-        with gpu_ctx.options(**_fused_opts(1, 32)):
-            dflt = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
-        for a_, b_ in zip(out, dflt):
-            assert np.array_equal(np.asarray(a_), np.asarray(b_))
-        # refused at every size: 24 x 24 regions at 180 angles (~5,600 rays) and 12 < 16 -> two passes
-        A, B, b, xt = _device_problem(gpu_ctx, 256, 180)
-        with gpu_ctx.options(fused_ab=0):
-            ref = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
-        with gpu_ctx.options(**_fused_opts(1, 24)):
-            with pytest.raises((ValueError, hgmres.HgmError)):   # HGM_E_ARG: no plan for the pair
-                hgmres.fused_plan_info(A, B)
-            out = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
-    else:
-        with gpu_ctx.options(**_fused_opts(0, 128)):
-            out = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
+    # the row-wave plan retries a refused region with half its side (round 5): 64 -> 32, the
+    # default plan, bit for bit
+    with gpu_ctx.options(**_fused_opts(1, 64)):
+        out = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
+    with gpu_ctx.options(**_fused_opts(1, 32)):
+        dflt = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
+    for a_, b_ in zip(out, dflt):
+        assert np.array_equal(np.asarray(a_), np.asarray(b_))
+    # refused at every size: 24 x 24 regions at 180 angles (~5,600 rays) and 12 < 16 -> two passes
+    A, B, b, xt = _device_problem(gpu_ctx, 256, 180)
+    with gpu_ctx.options(fused_ab=0):
+        ref = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
+    with gpu_ctx.options(**_fused_opts(1, 24)):
+        with pytest.raises((ValueError, hgmres.HgmError)):   # HGM_E_ARG: no plan for the pair
+            hgmres.fused_plan_info(A, B)
+        out = hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 8, ctx=gpu_ctx, return_H=True)
     for a_, b_ in zip(out, ref):
         assert np.array_equal(np.asarray(a_), np.asarray(b_))
 
@@ -206,7 +172,7 @@ def test_fused_not_taken_for_unmatched_or_reference_order(gpu_ctx):
     the option changes nothing there."""
     P = tomo_problem(32, 16, noise=1e-2, seed=0, backprojector="pixel")
     outs = []
-    for f, kd in ((0, 1), (1, 1)) + (((1, 0),) if _experiments() else ()):
+    for f, kd in ((0, 1), (1, 1)):
         with gpu_ctx.options(fused_ab=f, fused_kind=kd):
             outs.append(hgmres.ABgmres_nonhybrid_bounds(P.A, P.B, P.b, P.x_true, 0.0, 8, ctx=gpu_ctx, return_H=True))
     for o in outs[1:]:
@@ -214,10 +180,9 @@ def test_fused_not_taken_for_unmatched_or_reference_order(gpu_ctx):
             assert np.array_equal(np.asarray(a_), np.asarray(b_))
 
 
-@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("kind", [1])
 @pytest.mark.parametrize("world", [2, 4])
 def test_fused_on_pixel_shards(gpu_ctx, world, kind):
-    _variant_only_in_experiments(kind == 0)
     """The multi-GPU path (bench.py build_shard, DESIGN.md §5): rank g holds B_g = B(P_g,:), whole
     tile columns of the tiled pixels, and A_g = B_g'.  The one-pass A_g*(B_g*q) on each shard (its
     regions laid over the shard's window of pixel columns) matches the two-pass shard product, repeats
@@ -464,20 +429,36 @@ def test_fused_failed_plan_is_retried_with_other_options(gpu_ctx):
 
 
 def test_fused_dbg_refused_by_solvers(gpu_ctx):
-    """ADVICE r3: fused_dbg (phase-skipping timing variants, wrong results) is refused by every
-    solver; hgm_spmv_ab keeps it for scripts/fused_micro.py in the experiments build.  The default
-    library refuses the option value itself (VERDICT r5 weak #5)."""
-    A, B, b, xt = _device_problem(gpu_ctx, 64, 17)
-    if not _experiments():
-        with pytest.raises((ValueError, hgmres.HgmError), match="experiments build"):
-            gpu_ctx.set_option("fused_dbg", 1)
-        assert gpu_ctx.get_option("fused_dbg") == 0
-        return
-    with gpu_ctx.options(fused_dbg=1):
-        with pytest.raises(ValueError, match="fused_dbg"):
-            hgmres.ABgmres_nonhybrid_bounds(A, B, b, xt, 0.0, 4, ctx=gpu_ctx)
-        with pytest.raises(ValueError, match="fused_dbg"):
-            hgmres.lsqr_solver(A, b, xt, 0.0, 4, ctx=gpu_ctx, At=B)
+    """ADVICE r3: fused_dbg (phase-skipping timing variants, wrong results) could reach no solver.
+    The variants are retired and the library refuses the option value itself (VERDICT r5 weak #5)."""
+    with pytest.raises((ValueError, hgmres.HgmError), match="retired variant"):
+        gpu_ctx.set_option("fused_dbg", 1)
+    assert gpu_ctx.get_option("fused_dbg") == 0
+
+
+# option: (production value, the formerly legal variant values); DESIGN.md §3.5 has each measurement
+RETIRED = {"fused_region": (64, (8, 32, 128, 1024)), "fused_bs": (1024, (512,)), "fused_dbg": (0, (1, 2, 4, 7, 15)),
+           "fused_pf": (2, (0, 1, 3, 4)), "fused_kind": (1, (0,)), "fused_waves": (4, (1, 2)),
+           "fused_group": (8, (4,)), "fused_depth": (2, (3, 4)), "fused_pairs": (1, (0,)),
+           "fused_acc32": (1, (0, 2)), "fused_reduce": (0, (2, 3, 4)), "fused_rowpair": (4, (1, 2, 3)),
+           "fused_vsdepth": (3, (4,))}
+
+
+def test_retired_options_take_their_production_value_only(gpu_ctx):
+    """Options 19-22, 24, 26-30 and the variant values of 32, 34 and 38 selected measured variants of
+    the one-pass kernel, since retired.  The numbers stay: the production value is accepted, every
+    formerly legal variant value is refused (HGM_E_ARG, the retired message) and the option still
+    reads its production value.  No kernel runs."""
+    from hgmres import _lib as L
+    lib = L.load()
+    for name, (prod, variants) in RETIRED.items():
+        assert gpu_ctx.get_option(name) == prod, name
+        gpu_ctx.set_option(name, prod)
+        for v in variants:
+            assert lib.hgm_ctx_set_option(gpu_ctx.handle, L.option_id(name), float(v)) == L.HGM_E_ARG, (name, v)
+            with pytest.raises((ValueError, hgmres.HgmError), match="retired variant"):
+                gpu_ctx.set_option(name, v)
+            assert gpu_ctx.get_option(name) == prod, (name, v)
 
 
 @pytest.mark.parametrize("N,na,dtype,world", [(256, 47, None, 1), (512, 30, None, 1), (100, 17, None, 1),
@@ -514,7 +495,7 @@ def test_fused_reduce_by_band_is_bitwise(gpu_ctx, N, na, dtype):
     """The partial reduction by ray band (runs of consecutive slots, HGM_OPT_FUSED_REDUCE = 1)
     forms exactly the sums of the per-ray reduction through the slot list (= 0, the default):
     products, the AB-GMRES solve and the one-pass LSQR bit for bit.  The fewer-lanes-per-ray
-    variants (2, 3, 4: another fixed order, measured slower) are refused by the default library."""
+    variants (2, 3, 4: another fixed order, measured slower) are retired and refused."""
     from hgmres import _lib as L
     A = hgmres.SparseOperator.siddon(N, na, ctx=gpu_ctx, dtype=L.HGM_F32 if dtype else L.HGM_F64)
     B = A.T
@@ -532,24 +513,21 @@ def test_fused_reduce_by_band_is_bitwise(gpu_ctx, N, na, dtype):
             outs[red] = o
     for a_, b_ in zip(outs[0], outs[1]):
         assert np.array_equal(np.asarray(a_), np.asarray(b_))
-    if not _experiments():
-        for red in (2, 3, 4):
-            with pytest.raises((ValueError, hgmres.HgmError), match="experiments build"):
-                gpu_ctx.set_option("fused_reduce", red)
-        assert gpu_ctx.get_option("fused_reduce") == 0
+    for red in (2, 3, 4):
+        with pytest.raises((ValueError, hgmres.HgmError), match="retired variant"):
+            gpu_ctx.set_option("fused_reduce", red)
+    assert gpu_ctx.get_option("fused_reduce") == 0
 
 
 # ---------------------------------------------------------------------------------------------
-# Row pairs (HGM_OPT_FUSED_ROWPAIR, k_fused_rw RP, round 5): two consecutive pixel rows per
-# 128-entry chunk, each row parity into its own private accumulator array per wave.  Another
+# Row pairs (HGM_OPT_FUSED_ROWPAIR = 4, k_fused_rw PAIRS, round 5): two consecutive pixel rows per
+# 128-entry chunk (modes 1-3 are retired).  Another
 # fixed summation order: the same bars as the default pass (two-pass and oracle at 1e-10,
 # bitwise repeats; GKB in its production envelope), on geometries whose pairs overflow a chunk
 # (the plan cuts those runs) and ones that never do.
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,na,rp", [(256, 47, 1), (256, 47, 2), (256, 47, 3), (256, 47, 4), (512, 30, 4),
-                                     (100, 17, 4), (200, 60, 4), (2048, 19, 4)])
+@pytest.mark.parametrize("N,na,rp", [(256, 47, 4), (512, 30, 4), (100, 17, 4), (200, 60, 4), (2048, 19, 4)])
 def test_fused_rowpair_gmres_matches_oracle(gpu_ctx, N, na, rp):
-    _variant_only_in_experiments(rp in (1, 2, 3))
     A, B, b, xt = _device_problem(gpu_ctx, N, na)
     k = 20
     with gpu_ctx.options(fused_ab=0):
@@ -575,10 +553,9 @@ def test_fused_rowpair_gmres_matches_oracle(gpu_ctx, N, na, rp):
     assert rel(out[0], xo) <= TOL and hist_dev(out[1], eo) <= TOL and hist_dev(out[2], ro) <= TOL
 
 
-@pytest.mark.parametrize("rp", [1, 2, 3, 4])
+@pytest.mark.parametrize("rp", [4])
 @pytest.mark.parametrize("dtype", [None, "f32"])
 def test_fused_rowpair_gkb_matches_oracle(gpu_ctx, dtype, rp):
-    _variant_only_in_experiments(rp in (1, 2, 3))
     A, At, b, xt = _gkb_pair(gpu_ctx, 256, 47, dtype=dtype)
     k = 8 if dtype is None else 4
     with gpu_ctx.options(fused_ab=1, fused_rowpair=rp):

@@ -150,7 +150,7 @@ def test_vsdepth_not_carried_is_refused(gpu_ctx):
     missing = [d for d in (2, 3, 4) if d not in _carried(gpu_ctx)]
     assert missing and 2 not in missing and default not in missing
     for d in missing:
-        with pytest.raises((ValueError, hgmres.HgmError), match="experiments build"):
+        with pytest.raises((ValueError, hgmres.HgmError), match="retired variant"):
             gpu_ctx.set_option("fused_vsdepth", d)
     assert gpu_ctx.get_option("fused_vsdepth") == default
 
